@@ -4,13 +4,19 @@ refit -> traversal) on BASELINE config 2 (1 M uniform-random spheres, r = 0.001,
 radix-sort microbench of config 5 (64 Mi uint32 keys + uint32 ids) whose scatter pass carries
 the HBM roofline claim.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N = 1: one process, BASELINE config 2 (1 M spheres).  N > 1: launched by torch.distributed.run, one rank
 per GPU (RCCL); BASELINE config 4's workload -- every rank ARRIVES with the hash(id) mod N share of an
-(N x 2 M)-sphere uniform scene (16 M spheres at N = 8), see collision_amd/multi.py; the same run at
-1 M spheres per rank is reported beside it (`weak_1M_per_rank`).  Rank 0 prints ONE JSON line.  A "step"
-is one get_collisions (N = 1) / one DistributedCollider.step (N > 1) over device-resident inputs.
+(N x 2 M)-sphere uniform scene (16 M spheres at N = 8), see collision_amd/multi.py.  Rank 0 prints ONE JSON
+line.  A "step" is one get_collisions (N = 1) / one DistributedCollider.step (N > 1) over device-resident inputs.
+
+A plain run does only what the headline figure needs: set up, W untimed steps, K timed steps, the result line.
+--dump-outputs DIR then writes what the last timed step handed to its caller (dump_outputs below).
+--full adds every other leg to the same line: the radix-sort microbench and its roofline (with the rocprofv3
+PMC child passes), per-stage times, count-only mode, configs 3 / 4 / 5 and float64 on one GPU, the reference's
+benchmark shapes, the CPU baselines; at N > 1 the coherent-arrival run and the same protocol at 1 M spheres per
+rank (`weak_1M_per_rank`).  --no-cpu / --no-radix / --no-pmc drop legs of a --full run.
 """
 import argparse
 import json
@@ -404,6 +410,20 @@ def cpu_bruteforce_all_cores(n=100000):
             "extrapolated_seconds_at_1M": dt * (N_SPHERES / n) ** 2}
 
 
+def dump_outputs(out_dir, count, pairs, suffix=""):
+    """--dump-outputs: what the last timed step handed to its caller, as float64 .npy files (ids are exact there).
+    count<suffix>.npy is the pair count the step reported (the value behind `pairs_found` on one GPU; at N > 1 the
+    rank's own count) and pairs<suffix>.npy the (rows, 2) ids it stored, rows = min(count, capacity).  The order in
+    which a step appends its pairs to the buffer is not part of its contract (the tests compare sets), so the rows
+    are written in lexicographic order: two builds that find the same pairs write the same file."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    pairs = np.asarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    pairs = pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]
+    np.save(out_dir / ("count%s.npy" % suffix), np.array([count], dtype=np.float64))
+    np.save(out_dir / ("pairs%s.npy" % suffix), pairs.astype(np.float64))
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: run N ranks of this script under torch.distributed.run as a
     child process (never an exec: nothing here may replace a process that could hold the GPU) and return its
@@ -424,9 +444,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline legs")
-    ap.add_argument("--no-radix", action="store_true", help="skip the 64Mi-key radix microbench")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC child passes (roofline.traffic)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's pair count and pairs to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure (roofline, other configs, CPU baselines)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline legs")
+    ap.add_argument("--no-radix", action="store_true", help="--full: skip the 64Mi-key radix microbench")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 PMC child passes (roofline.traffic)")
     ap.add_argument("--partition", default="morton", choices=["morton", "hash"],
                     help="multi-GPU: repartition spatially (default) or keep the id-hash partition")
     args = ap.parse_args()
@@ -529,40 +553,46 @@ def main():
 
     if world == 1:
         pair_count = int(hip.read_buffer(cq, n_buf, np.uint32, 1)[0])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, pair_count,
+                         hip.read_buffer(cq, pairs_buf, np.uint32, (min(pair_count, PAIR_CAPACITY), 2)))
     else:
         pair_count = engine.global_pair_count()
+        if args.dump_outputs:                 # every rank writes the pairs it found itself (global ids)
+            dump_outputs(args.dump_outputs, engine.engine.pair_count(), engine.local_pairs(), "_rank%d" % rank)
         extra["dist_backend"] = dist.get_backend()
         extra["world_size_seen"] = dist.get_world_size()
         extra["per_rank"] = {"owned_spheres_rank0": engine.stats.get("owned"), "ghost_queries_rank0": engine.stats.get("ghosts"),
                              "partition_slot_records": engine.stats.get("partition_slot"),
                              "halo_slot_records": engine.stats.get("halo_slot"), "repeated_steps": engine.repeats}
-        # the same spheres with a coherent arrival: each step's input is what the rank owned after the previous one
-        # (adopt_owned: a simulation advancing positions in place).  Nothing has moved, so after the first step every
-        # sphere is kept by its rank and the repartition slots travel nearly empty.  NOT the headline workload.
-        def coherent_step():
-            engine.adopt_owned()
-            engine.step()
-        dtc = timed_region(coherent_step, engine.synchronize)
-        extra["coherent_arrival"] = {"workload": "%d x 2M spheres, input of a step = owned spheres of the previous one" % world,
-                                     "ms_per_step": round(dtc / args.steps * 1e3, 4),
-                                     "m_spheres_per_s": round(N_PER_RANK_MULTI * world / (dtc / args.steps) / 1e6, 2),
-                                     "partition_slot_records": engine.stats.get("partition_slot"),
-                                     "pairs_found": engine.global_pair_count()}
-        # the same protocol at 1 M spheres per rank (round 1's line), reported beside the config-4 workload
-        del engine
-        engine1 = make_engine(N_SPHERES)
-        dt1 = timed_region(engine1.step, engine1.synchronize)
-        extra["weak_1M_per_rank"] = {"workload": "%d x 1M spheres, same protocol" % world, "ms_per_step": round(dt1 / args.steps * 1e3, 4),
-                                     "m_spheres_per_s": round(N_SPHERES * world / (dt1 / args.steps) / 1e6, 2),
-                                     "pairs_found": engine1.global_pair_count()}
-        cq = engine1.cq
+        if args.full:
+            # the same spheres with a coherent arrival: each step's input is what the rank owned after the previous one
+            # (adopt_owned: a simulation advancing positions in place).  Nothing has moved, so after the first step every
+            # sphere is kept by its rank and the repartition slots travel nearly empty.  NOT the headline workload.
+            def coherent_step():
+                engine.adopt_owned()
+                engine.step()
+            dtc = timed_region(coherent_step, engine.synchronize)
+            extra["coherent_arrival"] = {"workload": "%d x 2M spheres, input of a step = owned spheres of the previous one" % world,
+                                         "ms_per_step": round(dtc / args.steps * 1e3, 4),
+                                         "m_spheres_per_s": round(N_PER_RANK_MULTI * world / (dtc / args.steps) / 1e6, 2),
+                                         "partition_slot_records": engine.stats.get("partition_slot"),
+                                         "pairs_found": engine.global_pair_count()}
+            # the same protocol at 1 M spheres per rank (round 1's line), reported beside the config-4 workload
+            del engine
+            engine1 = make_engine(N_SPHERES)
+            dt1 = timed_region(engine1.step, engine1.synchronize)
+            extra["weak_1M_per_rank"] = {"workload": "%d x 1M spheres, same protocol" % world, "ms_per_step": round(dt1 / args.steps * 1e3, 4),
+                                         "m_spheres_per_s": round(N_SPHERES * world / (dt1 / args.steps) / 1e6, 2),
+                                         "pairs_found": engine1.global_pair_count()}
+            cq = engine1.cq
     extra["pairs_found"] = pair_count
 
     result = None
     if rank == 0:
         roofline = None
         rb = None
-        if not args.no_radix:
+        if args.full and not args.no_radix:
             # the dominant kernel is the same on every rank: rank 0 measures it live at any N
             try:
                 rb = radix_microbench(hip, ctx, cq)
@@ -609,7 +639,7 @@ def main():
                 roofline["traffic"], roofline["traffic_detail"] = pmc_traffic()
                 roofline["traffic_source"] = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE child passes of tools/radix_only.py in this "
                                               "run; bytes = (2 * FETCH + WRITE) * 1024")
-        if world == 1:
+        if world == 1 and args.full:
             # per-stage device times of the 1M path (HIP events on the launch stream)
             from collision_amd.stages import stage_times
             extra["stage_ms"] = stage_times(hip, ctx, cq, collider, coords_buf, radii_buf, n_buf, pairs_buf,
@@ -630,7 +660,7 @@ def main():
                 extra["config4_whole_scene_on_one_gpu"] = single_gpu_leg(hip, ctx, cq, 8 * N_PER_RANK_MULTI, reps=5)
                 extra["reference_benchmark_shapes_ms"] = reference_benchmark_shapes(hip, ctx, cq)
         cpu = None
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             cpu = cpu_baseline(coords, radii)
             extra["cpu_bruteforce_config1"] = cpu_bruteforce_10k()
             extra["cpu_bruteforce_all_cores"] = cpu_bruteforce_all_cores()

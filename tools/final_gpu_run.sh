@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-end GPU runs (from the repo root on the GPU box).  Each mode is one gpurun call within the 1200 s limit:
-#   bash tools/final_gpu_run.sh tests       GPU test suite, bench.py (default flags), N=2 gloo rehearsal of the bench
+#   bash tools/final_gpu_run.sh tests       GPU test suite, bench.py --full (default sizes), N=2 gloo rehearsal of the bench
 #   bash tools/final_gpu_run.sh profiles    rocprofv3 kernel-trace stats of bench.py + PMC passes (radix 64 Mi, 1 M path)
 #   bash tools/final_gpu_run.sh profiles2   the HBM-bound regime (2 M / 16 M), the traversal before / after leaf blocks, config 4
 # The rocprofv3 databases are condensed ON THE BOX (tools/summarize_prof.py) into gpurun_out/summary/ and deleted: gpurun
@@ -14,10 +14,10 @@ cd $R
 if [ "$1" = "tests" ]; then
     timeout -k 10 800 python -m pytest tests -m gpu -x -q --durations=10 > $O/final_tests.log 2>&1 || { tail -30 $O/final_tests.log; exit 1; }
     tail -14 $O/final_tests.log
-    timeout -k 10 300 python bench.py > $O/bench_final.json 2> $O/bench_final.err || { tail -20 $O/bench_final.err; exit 1; }
+    timeout -k 10 300 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err || { tail -20 $O/bench_final.err; exit 1; }
     echo "bench ok"
     # typed as a plain command: bench.py starts its own torch.distributed.run (gloo here: both ranks share this box's GPU)
-    COLLISION_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 10 --warmup 3 --no-radix > $O/bench_g2.json 2> $O/bench_g2.err \
+    COLLISION_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 10 --warmup 3 --no-radix > $O/bench_g2.json 2> $O/bench_g2.err \
         || { tail -20 $O/bench_g2.err; exit 1; }
     echo "gloo N=2 rehearsal ok"
     exit 0
@@ -30,7 +30,7 @@ pmc_pass() {      # pmc_pass <out dir> <counters> <script and args...>
 }
 if [ "$1" = "profiles" ]; then
     rm -rf $O/prof_bench
-    ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o bench -- python3 $R/bench.py --no-cpu --no-pmc > $O/prof_bench.log 2>&1 ) \
+    ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o bench -- python3 $R/bench.py --full --no-cpu --no-pmc > $O/prof_bench.log 2>&1 ) \
         || { tail -20 $O/prof_bench.log; exit 1; }
     python tools/summarize_prof.py stats $O/prof_bench/bench_results.db > $S/bench_kernel_stats.txt && rm -rf $O/prof_bench
     echo "rocprof stats ok"
