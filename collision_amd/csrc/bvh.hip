@@ -1484,7 +1484,8 @@ size_t col_collide_scratch_bytes(uint32_t n, uint32_t padded, int coord_bytes) {
     return 256 /* scene range */ + col_reduce_scratch_bytes(coord_bytes == 8 ? COL_F64 : COL_F32, 4) +
            col_radix_scratch_bytes(padded, 4, 4) + col_lbvh_scratch_bytes(n, coord_bytes) +
            (size_t)n * 4 * coord_bytes /* packed (x,y,z,r) rows */ + sizeof(ChunkHdr) + 256 /* chunked pair allocation */ + 1024 +
-           8 * ((size_t)n / 64 + 1) + 256 /* walk order: cost[] + perm[] */;
+           8 * ((size_t)n / 64 + 1) + 256 /* walk order: cost[] + perm[] */ +
+           256 + col_radix_msd_fused_bytes() /* the MSD pass without a scan launch: group sums + bucket starts */;
 }
 
 int col_collide(void *stream, const void *coords, const void *radii, uint32_t n, uint32_t padded, int coord_bytes,
@@ -1543,7 +1544,9 @@ int col_collide_plan_dev(void *stream, const void *coords, const void *radii, ui
     p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
     void *packed = p;          p += (size_t)n * 4 * coord_bytes;
     p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-    void *chunk_hdr = p;
+    void *chunk_hdr = p;       p += sizeof(ChunkHdr) + 256 + 8 * ((size_t)n / 64 + 1) + 256;     // header, packet counters, walk order
+    p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
+    uint32_t *msd_fused = (uint32_t *)p;       // group sums (zero before the Morton kernel, in every call) + bucket starts
     // sort_plan: bit 0 = the sort (COL_SORT_LSD / COL_SORT_MSD), bit 1 = COL_TRAVERSE_CHUNKED (dense scenes)
     const bool chunked = (sort_plan & COL_TRAVERSE_CHUNKED) != 0;
     sort_plan &= 1;
@@ -1556,14 +1559,19 @@ int col_collide_plan_dev(void *stream, const void *coords, const void *radii, ui
         // counts the digits of the sort's first pass (the histogram sits at the start of the sort scratch): two
         // launches less.  The MSD plan (one global pass + an LDS finish per bucket) applies up to COL_MSD_MAX_N.
         const bool msd = sort_plan == COL_SORT_MSD && padded <= COL_MSD_MAX_N;
+        // MSD: no scan launch either -- the Morton kernel also adds its counts into group sums and the pass works out its own
+        // offsets (radix.hip, k_scatter FUSED).  The group sums are cleared by the bounds kernel when it runs here, else by a memset.
+        const uint32_t nsums = msd ? (uint32_t)(col_radix_msd_fused_bytes() / sizeof(uint32_t)) : 0u;
+        if (msd && col_ceil_div(padded, tile) > (uint64_t)COL_MSD_GROUP * COL_MSD_GROUPS) return COL_EINVAL;    // (more tiles than group sums: no tile class does that)
         if (!partials) {
-            if ((rc = col_minmax4_stage1(stream, coords, n, coord_bytes, red_scratch, &parts))) return rc;
+            if ((rc = col_minmax4_stage1_zero(stream, coords, n, coord_bytes, red_scratch, &parts, msd_fused, nsums))) return rc;
             partials = red_scratch;
-        }
+        } else if (msd)
+            COL_HIP(hipMemsetAsync(msd_fused, 0, nsums * sizeof(uint32_t), s));
         if ((rc = col_morton_tile(stream, coords, radii, partials, parts, n, padded, coord_bytes, codes0, ids0, packed,
                                   counter, (uint32_t *)sort_scratch, tile, (uint32_t)col_ceil_div(padded, tile), msd ? 22 : 0,
-                                  publish, n_dev))) return rc;
-        if (msd) rc = col_radix_sort_msd_dev(stream, codes0, codes1, ids0, ids1, padded, sort_scratch, oversize, n_dev);
+                                  publish, n_dev, msd ? msd_fused : nullptr))) return rc;
+        if (msd) rc = col_radix_sort_msd_fused(stream, codes0, codes1, ids0, ids1, padded, sort_scratch, oversize, n_dev, msd_fused);
         else rc = col_radix_sort_ex(stream, codes0, codes1, ids0, ids1, padded, 4, 4, sort_scratch, 0, 1);
         if (rc) return rc;
         // the LSD plan was taken where the MSD plan could apply: tell the caller how clustered the codes are (oversize[1])

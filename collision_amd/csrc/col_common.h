@@ -43,7 +43,9 @@ extern "C" int col_radix_sort_msd_dev(void *stream, const uint32_t *keys, uint32
 //  * col_morton_tile: col_morton_ex that folds those partials itself (no stage-2 launch) and also
 //    writes a histogram for the radix sort (digit = bits hist_shift..hist_shift+7: 0 for the LSD sort's
 //    pass 0, 22 for the MSD sort's bucket digit), `tile` = 1024 or 4096 codes per block (the sort's
-//    tile, col_radix_tile), digit-major hist[d * nblocks + b] like k_hist;
+//    tile, col_radix_tile), digit-major hist[d * nblocks + b] like k_hist; with `gsum` (the MSD plan without a scan launch,
+//    col_radix_sort_msd_fused) tile-major hist[b * 256 + d] instead, each count also added into gsum[(b / COL_MSD_GROUP) * 256 + d],
+//    which must be zero on entry (col_minmax4_stage1_zero clears it in the launch before);
 //  * col_radix_sort_ex(have_hist0 = 1): col_radix_sort that finds the pass-0 histogram already at the
 //    start of `scratch`.
 #define COL_MINMAX_PARTS 256
@@ -60,7 +62,14 @@ extern "C" int col_minmax4_stage1_dev(void *stream, const void *rows, const uint
 extern "C" int col_morton_tile(void *stream, const void *coords, const void *radii, const void *partials, uint32_t parts,
                                uint32_t n, uint32_t padded, int coord_bytes, uint32_t *codes, uint32_t *ids, void *packed,
                                uint32_t *zero_word, uint32_t *hist0, uint32_t tile, uint32_t nblocks, int hist_shift,
-                               uint32_t *publish, const uint32_t *n_dev);
+                               uint32_t *publish, const uint32_t *n_dev, uint32_t *gsum);
+#define COL_MSD_GROUP 32u       /* tiles per group sum of the fused MSD pass (radix.hip: MSD_GROUP) */
+#define COL_MSD_GROUPS 32u      /* group sums per digit: the fused pass takes at most COL_MSD_GROUP * COL_MSD_GROUPS tiles */
+extern "C" int col_minmax4_stage1_zero(void *stream, const void *rows, uint64_t n, int coord_bytes, void *partials, uint32_t *parts,
+                                       uint32_t *zero, uint32_t nzero);      // col_minmax4_stage1 that also clears nzero words at `zero`
+extern "C" size_t col_radix_msd_fused_bytes(void);
+extern "C" int col_radix_sort_msd_fused(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out,
+                                        uint64_t n, void *scratch, uint32_t *oversize, const uint32_t *n_real_dev, uint32_t *fused);
 extern "C" int col_radix_sort_ex(void *stream, const void *keys, void *keys_out, const void *vals, void *vals_out,
                                  uint64_t n, int key_bytes, int val_bytes, void *scratch, int copy_back, int have_hist0);
 

@@ -18,10 +18,11 @@
 //             box; every node is written as one 32-byte record (box + traversal links) per thread.
 //             A node that crosses the chunk boundary stores the half of its range that lies in this
 //             chunk (`partial`: the prefix / suffix unions of the chunk's leaf boxes).
-//   k_group   (1-2 tiny launches) sparse tables over chunk totals, 256 chunks per group,
-//             then over group totals, ...
-//   k_cross   the ~1-2 % of nodes that cross chunks: partial[first] U partial[last] U
-//             O(1) table look-ups for the whole chunks in between.  k_chunk lists them per chunk (CROSS_CAP words),
+//   k_group   (above COL_MSD_MAX_N / 256 chunks only; 1-2 tiny launches) sparse tables over chunk totals,
+//             256 chunks per group, then over group totals, ...
+//   k_cross   the ~1-2 % of nodes that cross chunks: partial[first] U partial[last] U the whole chunks in
+//             between -- read straight from the chunk totals k_chunk wrote (short ranges by the node's thread,
+//             longer ones by a wave or by the whole workgroup), or, where k_group ran, O(1) table look-ups.  k_chunk lists them per chunk (CROSS_CAP words),
 //             k_cross runs one thread per list slot (round 3: 76 -> 43 us at 16 M spheres; a thread per NODE left
 //             one or two busy lanes per wave).
 //
@@ -970,9 +971,126 @@ __device__ __forceinline__ void cross_node(T *__restrict__ bounds, const u32 *__
     row[4] = box.hi[0]; row[5] = box.hi[1]; row[6] = box.hi[2];
 }
 
+// The direct form (DIRECT, up to CROSS_DIRECT_MAX_CHUNKS chunks): no tables, so no k_group launch.  The whole chunks strictly
+// between a crossing node's two ends are read from the chunk totals themselves (level 0 of the first table, written by k_chunk
+// before this launch).  The crossing nodes are a laminar family, so all their ranges together are about nchunks * log2(nchunks)
+// boxes (47 k x 32 B at 1 M spheres) -- less than the tables k_group would write.  Min / max are idempotent: reading an entry
+// twice (the clamped loads below) cannot change a bit.
+constexpr u32 CROSS_SHORT = 8;                            // a range of at most this many chunks: the slot's own thread reads it
+constexpr u32 CROSS_LIST = (256 / CROSS_CAP) * C;         // longer ranges of a workgroup, at most every node of its 8 chunks
+#ifndef COL_CROSS_DIRECT_MAX_N       /* (-DCOL_CROSS_DIRECT_MAX_N=0: a build that keeps k_group everywhere, for A/Bs of two libraries) */
+#define COL_CROSS_DIRECT_MAX_N COL_MSD_MAX_N
+#endif
+constexpr u32 CROSS_DIRECT_MAX_CHUNKS = COL_CROSS_DIRECT_MAX_N / C;
+
+// chunk e's total box: level-0 entry e of the first table, [group][level][256]
+__device__ __forceinline__ uint64_t chunk_total_at(u32 e) { return (uint64_t)(e / C) * (LV * C) + e % C; }
+
+template <typename T>
+__device__ __forceinline__ void cross_store(T *__restrict__ bounds, u32 i, const Box<T> &box) {
+    // links (lane w) were written by k_chunk: store xyz only
+    T *row = bounds + 8ull * i;
+    row[0] = box.lo[0]; row[1] = box.lo[1]; row[2] = box.lo[2];
+    row[4] = box.hi[0]; row[5] = box.hi[1]; row[6] = box.hi[2];
+}
+
+// CROSS_MID: the longest range one wave reads in a single round trip (CROSS_MID_U entries in flight per lane); anything longer is
+// read by the whole workgroup, CrossU<T>::U entries per thread and round trip (the root of a 1 M scene: 3905 entries, 15.3 per thread)
+template <typename T> struct CrossU { static constexpr u32 U = sizeof(T) == 4 ? 16 : 8; };
+constexpr u32 CROSS_MID_U = 8, CROSS_MID = COL_WAVE * CROSS_MID_U;
+struct CrossLds {
+    uint2 list[CROSS_LIST];                       // (node, other end): wave-sized ranges from the front, longer ones from the back
+    u32 nmid, nhuge;
+    double part[256 / COL_WAVE][6];               // the waves' results for a huge node
+};
+
+// node i with a short range is finished here; a longer one is listed for the waves of the workgroup / the workgroup
+template <typename T>
+__device__ __forceinline__ void cross_direct(T *__restrict__ bounds, const u32 *__restrict__ other_end, const T *__restrict__ partial,
+                                             const T *__restrict__ tab0, u32 i, CrossLds &lds) {
+    const u32 j = other_end[i];
+    const u32 first = min(i, j), last = max(i, j);
+    const u32 a = first / C + 1, b = last / C;             // whole chunks [a, b) strictly between the two ends
+    if (b < a) return;                                     // both ends in one chunk: k_chunk finished this node
+    if (b - a > CROSS_MID) { lds.list[CROSS_LIST - 1 - atomicAdd(&lds.nhuge, 1u)] = make_uint2(i, j); return; }
+    if (b - a > CROSS_SHORT) { lds.list[atomicAdd(&lds.nmid, 1u)] = make_uint2(i, j); return; }
+    Box<T> box = box_load(partial, first);
+    box_merge(box, box_load(partial, last));
+    if (b > a) {
+        Box<T> v[CROSS_SHORT];
+#pragma unroll
+        for (u32 k = 0; k < CROSS_SHORT; k++) v[k] = box_load(tab0, chunk_total_at(min(a + k, b - 1)));    // independent loads, one round trip
+#pragma unroll
+        for (u32 k = 0; k < CROSS_SHORT; k++) box_merge(box, v[k]);
+    }
+    cross_store(bounds, i, box);
+}
+
+template <typename T> __device__ __forceinline__ void box_wave_union(Box<T> &box) {
+#pragma unroll
+    for (int o = COL_WAVE / 2; o > 0; o >>= 1) {
+        Box<T> r;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { r.lo[k] = __shfl_xor(box.lo[k], o, COL_WAVE); r.hi[k] = __shfl_xor(box.hi[k], o, COL_WAVE); }
+        box_merge(box, r);
+    }
+}
+
+// entries e0, e0 + stride, ... (U of them, all loads issued before the first use; clamped to b - 1) merged into box
+template <typename T, u32 U>
+__device__ __forceinline__ void cross_batch(const T *__restrict__ tab0, u32 e0, u32 stride, u32 b, Box<T> &box) {
+    Box<T> v[U];
+#pragma unroll
+    for (u32 k = 0; k < U; k++) v[k] = box_load(tab0, chunk_total_at(min(e0 + stride * k, b - 1)));
+#pragma unroll
+    for (u32 k = 0; k < U; k++) box_merge(box, v[k]);
+}
+
+// a listed node of up to CROSS_MID chunks, one per wave: one round trip
+template <typename T>
+__device__ __forceinline__ void cross_direct_wave(T *__restrict__ bounds, const T *__restrict__ partial,
+                                                  const T *__restrict__ tab0, uint2 ij, u32 lane) {
+    const u32 first = min(ij.x, ij.y), last = max(ij.x, ij.y);
+    const u32 a = first / C + 1, b = last / C;
+    Box<T> box = box_load(partial, first);
+    box_merge(box, box_load(partial, last));
+    cross_batch<T, CROSS_MID_U>(tab0, a + lane, COL_WAVE, b, box);
+    box_wave_union(box);
+    if (lane == 0) cross_store(bounds, ij.x, box);
+}
+
+// a listed node of more than CROSS_MID chunks, by the whole workgroup (uniform control flow: barriers inside)
+template <typename T>
+__device__ __forceinline__ void cross_direct_block(T *__restrict__ bounds, const T *__restrict__ partial,
+                                                   const T *__restrict__ tab0, uint2 ij, CrossLds &lds) {
+    constexpr u32 U = CrossU<T>::U;
+    const u32 tid = threadIdx.x, lane = tid % COL_WAVE, w = tid / COL_WAVE;
+    const u32 first = min(ij.x, ij.y), last = max(ij.x, ij.y);
+    const u32 a = first / C + 1, b = last / C;
+    Box<T> box = box_load(partial, first);
+    box_merge(box, box_load(partial, last));
+    for (u32 e0 = a; e0 < b; e0 += 256 * U) cross_batch<T, U>(tab0, e0 + tid, 256, b, box);      // (b - a > CROSS_MID: every thread has an entry)
+    box_wave_union(box);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { lds.part[w][k] = (double)box.lo[k]; lds.part[w][3 + k] = (double)box.hi[k]; }     // (exact: T is float or double)
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (u32 ww = 1; ww < 256 / COL_WAVE; ww++) {
+            Box<T> o;
+#pragma unroll
+            for (int k = 0; k < 3; k++) { o.lo[k] = (T)lds.part[ww][k]; o.hi[k] = (T)lds.part[ww][3 + k]; }
+            box_merge(box, o);
+        }
+        cross_store(bounds, ij.x, box);
+    }
+    __syncthreads();
+}
+
 // One thread per (chunk, list slot): CROSS_CAP threads per chunk instead of one per node -- a wave of the per-node version
 // had one or two crossing nodes among its 64 and ran their table look-ups at that utilisation (76 us at 16 M spheres).
-template <typename T>
+template <typename T, bool DIRECT = false>
 __global__ __launch_bounds__(256) void k_cross(T *__restrict__ bounds, const u32 *__restrict__ other_end,
                                                const T *__restrict__ partial, const u32 *__restrict__ cross, Tabs tabs, u32 n,
                                                u32 nchunks, int lin, u32 *__restrict__ zero8, const u32 *__restrict__ n_dev,
@@ -986,6 +1104,31 @@ __global__ __launch_bounds__(256) void k_cross(T *__restrict__ bounds, const u32
     const u32 t = blockIdx.x * 256 + threadIdx.x;
     if (zero8 && t < nzero) zero8[t] = 0;      // the packet counters (or the whole chunk header) of the traversal that follows (bvh.hip), no launch of their own
     const u32 chunk = t / CROSS_CAP, slot = t % CROSS_CAP;
+    if constexpr (DIRECT) {
+        // every entry read below belongs to a chunk under the real chunk count: the ranges are those of real nodes
+        // (listed by a real chunk's k_chunk workgroup, or i + 1 < n), and a node's last leaf is below n
+        __shared__ CrossLds lds;
+        const T *tab0 = (const T *)tabs.t[0];
+        if (threadIdx.x == 0) { lds.nmid = 0; lds.nhuge = 0; }
+        __syncthreads();
+        if (chunk < nchunks) {
+            if (cross[(uint64_t)chunk * CROSS_CAP + CROSS_CAP - 1] == CROSS_DENSE) {
+                for (u32 k = slot; k < (u32)C; k += CROSS_CAP) {
+                    const u32 i = chunk * C + k;
+                    if (i + 1 < n) cross_direct(bounds, other_end, partial, tab0, i, lds);
+                }
+            } else {
+                const u32 i = cross[(uint64_t)chunk * CROSS_CAP + slot];
+                if (i != END) cross_direct(bounds, other_end, partial, tab0, i, lds);
+            }
+        }
+        __syncthreads();
+        const u32 nhuge = lds.nhuge, nmid = lds.nmid;
+        for (u32 q = 0; q < nhuge; q++) cross_direct_block(bounds, partial, tab0, lds.list[CROSS_LIST - 1 - q], lds);
+        for (u32 q = threadIdx.x / COL_WAVE; q < nmid; q += 256 / COL_WAVE)
+            cross_direct_wave(bounds, partial, tab0, lds.list[q], threadIdx.x % COL_WAVE);
+        return;
+    }
     if (chunk >= nchunks) return;
     if (cross[(uint64_t)chunk * CROSS_CAP + CROSS_CAP - 1] == CROSS_DENSE) {
         for (u32 k = slot; k < (u32)C; k += CROSS_CAP) {
@@ -999,6 +1142,9 @@ __global__ __launch_bounds__(256) void k_cross(T *__restrict__ bounds, const u32
 }
 
 int g_dbg = 0;         // process-wide diagnostics switch (col_debug_lbvh); see include/collision_hip.h
+// col_debug_lbvh bits that select a production instance or a host-side choice, not the diagnostics instance of k_chunk
+constexpr int DBG_TABLES = 32768;       // k_group + the table look-ups in k_cross at every size (tests, A/Bs)
+constexpr int DBG_PLAIN = 1024 | 2048 | 4096 | 8192 | 16384 | DBG_TABLES;
 float g_block_k = 3.0f;   // leaf-block density criterion (col_debug_leaf_blocks): node width <= k x leaf width; 0 = no marks
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -1041,9 +1187,9 @@ int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const 
     // delta() -- for A/Bs (tools/lbvh_scan_ab.py)
     // (bit 11 (2048), likewise: float64 keeps the shuffle scans -- the A/B of the float64 DPP scans)
     // (bit 12 (4096): the traversal's walk order is used whatever the previous costs look like -- tests)
-    if (g_dbg & ~(1024 | 2048 | 4096 | 8192 | 16384))          // (bit 14: 24 KB of unused LDS per workgroup -- half the resident workgroups: a timing experiment)
+    if (g_dbg & ~DBG_PLAIN)          // (bit 14: 24 KB of unused LDS per workgroup -- half the resident workgroups: a timing experiment)
         k_chunk<T, true, int64_t><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
-                                                                    (T *)tabs.t[0], n, (T)g_block_k, n_dev, ChunkDiagOn{g_dbg & ~(1024 | 2048 | 4096 | 8192 | 16384)});
+                                                                    (T *)tabs.t[0], n, (T)g_block_k, n_dev, ChunkDiagOn{g_dbg & ~DBG_PLAIN});
     else if (n < (1u << 30) && (g_dbg & 8192))         // (bit 13: Karras' searches for every node -- the A/B of the climb)
         k_chunk<T, false, int32_t, true, true><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
                                                                                  (T *)tabs.t[0], n, (T)g_block_k, n_dev, ChunkDiagOff{});
@@ -1073,6 +1219,14 @@ int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const 
         if (zero8) COL_HIP(hipMemsetAsync(zero8, 0, nzero * sizeof(u32), s));
         return COL_OK;
     }
+    const unsigned cross_blocks = (unsigned)col_ceil_div((uint64_t)nchunks * CROSS_CAP, 256);
+    const dim3 cross_grid(cross_blocks + (walk_order && !ordered_by_chunk ? 8u * COL_ORDER_SLICES : 0u));
+    if (nchunks <= CROSS_DIRECT_MAX_CHUNKS && !(g_dbg & DBG_TABLES)) {     // k_cross reads the chunk totals itself: no tables, no k_group
+        k_cross<T, true><<<cross_grid, dim3(256), 0, s>>>(bounds, other_end, partial, cross, tabs, n, nchunks, -1, zero8,
+                                                          n_dev, walk_order, cross_blocks, order_mode, nzero);
+        COL_LAUNCH_OK();
+        return COL_OK;
+    }
     int lin = -1;
     for (int h = 0; h < 3; h++) {
         if (h > 0 && L.count[h] <= LIN) { lin = h; break; }      // k_cross scans this level's few entries itself
@@ -1081,9 +1235,8 @@ int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const 
         COL_LAUNCH_OK();
         if (groups < 2) break;
     }
-    const unsigned cross_blocks = (unsigned)col_ceil_div((uint64_t)nchunks * CROSS_CAP, 256);
-    k_cross<T><<<dim3(cross_blocks + (walk_order && !ordered_by_chunk ? 8u * COL_ORDER_SLICES : 0u)), dim3(256), 0, s>>>(bounds, other_end, partial, cross, tabs, n, nchunks, lin, zero8,
-                                                                                                          n_dev, walk_order, cross_blocks, order_mode, nzero);
+    k_cross<T><<<cross_grid, dim3(256), 0, s>>>(bounds, other_end, partial, cross, tabs, n, nchunks, lin, zero8,
+                                                n_dev, walk_order, cross_blocks, order_mode, nzero);
     COL_LAUNCH_OK();
     return COL_OK;
 }

@@ -217,11 +217,29 @@ template <int SCOPE, typename X> __device__ __forceinline__ void st_scope(X *p, 
 // ---- scatter ----
 template <bool NARROW> struct CntType { typedef u32 T; };
 template <> struct CntType<true> { typedef uint16_t T; };
-template <typename K, int VB, int IT, int NT, bool DIAG>
+// FUSED (the MSD pass inside col_collide, col_radix_sort_msd_fused below): there is no scan launch in front of the pass.
+// `offsets` then holds the UNSCANNED counts, tile-major (count of digit d in tile b at [b * 256 + d]), and gsum[g * 256 + d] their
+// sums over group g of MSD_GROUP consecutive tiles, both written by col_morton_tile.  Thread d of tile b adds up its offset itself:
+// the totals of the digits below d (a block scan over the digits' totals, each the sum of a digit's group sums), the group sums
+// below its group and the tiles of its own group below b -- MSD_GROUPS + MSD_GROUP - 1 words per thread, every load of a wave one
+// contiguous 256-byte piece, all issued where the one offset load of the scanned form is issued and first used after the ranking.
+// Tile 0 leaves the 256 bucket starts in starts[] for k_bucket_sort.
+constexpr int MSD_GROUP = COL_MSD_GROUP, MSD_GROUPS = COL_MSD_GROUPS;      // up to 1024 tiles: every size of the MSD plan (col_radix_tile)
+// (the two tile classes of the MSD plan: below SMALL_N pairs 1024-pair tiles, up to COL_MSD_MAX_N 4096-pair ones; col_collide_plan_dev
+// checks the tile count again before it launches the Morton kernel that writes the group sums)
+static_assert((uint64_t)NT_SMALL * IT_SMALL * MSD_GROUP * MSD_GROUPS >= (1u << 20) && (uint64_t)NT_MID * IT_BIG * MSD_GROUP * MSD_GROUPS >= COL_MSD_MAX_N,
+              "the group sums cover every tile count of the MSD plan");
+struct FusedOff {};
+struct FusedOn { const u32 *gsum; u32 *starts; };
+template <bool FUSED> struct FusedArg { typedef FusedOff T; };
+template <> struct FusedArg<true> { typedef FusedOn T; };
+template <typename K, int VB, int IT, int NT, bool DIAG, bool FUSED = false>
 __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K *__restrict__ keys_out,
                                                 const void *__restrict__ vals_in_, void *__restrict__ vals_out_,
                                                 uint64_t n, u32 nblocks, int shift,
-                                                const u32 *__restrict__ offsets, typename DiagArg<DIAG>::T diag) {
+                                                const u32 *__restrict__ offsets, typename DiagArg<DIAG>::T diag,
+                                                typename FusedArg<FUSED>::T fused = {}) {
+    static_assert(!FUSED || (NT == RDIG && !DIAG), "the fused form: one thread per digit, production instance only");
     const int dbg = diag_mode(diag);        // the constant 0 in the production instance
     constexpr int TILE = NT * IT;
     constexpr int NW = NT / COL_WAVE;
@@ -266,7 +284,10 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
     if (DIAG && (dbg & (1 << 27))) __builtin_amdgcn_s_setprio(3);
     // this tile's global offset of digit `tid`: one scattered 4-byte load per thread, issued now so that
     // its latency hides under the loads and the ranking instead of sitting between two barriers
-    const u32 my_offset = tid < RDIG ? offsets[(uint64_t)tid * nblocks + b] : 0u;
+    // (FUSED: the words this thread adds up instead, see above the kernel -- issued at the same point, inside the branches below)
+    u32 my_offset = 0;
+    u32 fused_below = 0, fused_total = 0;       // group sums and tile counts below this tile; the digit's total
+    if constexpr (!FUSED) my_offset = tid < RDIG ? offsets[(uint64_t)tid * nblocks + b] : 0u;
     for (u32 i = tid; i < NW * RDIG; i += NT) (&s_cnt[0][0])[i] = (CNT)0;
 
     const u32 wbase = w * (COL_WAVE * IT) + lane;
@@ -287,6 +308,14 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
         // round trip per tile instead of two.  Round 4: the wave then waits for its KEYS only -- vmcnt counts in
         // issue order, the NVQ value loads were issued after them -- and ranks them while the values are still on
         // their way; the values are waited for, transposed and taken into registers after the ranking.
+        u32 gs[FUSED ? MSD_GROUPS : 1], hs[FUSED ? MSD_GROUP - 1 : 1];
+        if constexpr (FUSED) {
+            const u32 b0 = b & ~(u32)(MSD_GROUP - 1);
+#pragma unroll
+            for (int g = 0; g < MSD_GROUPS; g++) gs[g] = (fused.gsum + g * RDIG)[tid];      // (uniform row + lane: scalar base addresses)
+#pragma unroll
+            for (int t = 0; t < MSD_GROUP - 1; t++) hs[t] = (offsets + (size_t)min(b0 + t, nblocks - 1) * RDIG)[tid];    // (used below b only)
+        }
         K *stage = s_keys + w * (COL_WAVE * IT);
         const K *src = keys_in + tile_base + w * (COL_WAVE * IT);
         const V *vsrc = vals_in + tile_base + w * (COL_WAVE * IT);
@@ -325,7 +354,42 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int k = 0; k < IT; k++) key[k] = stage[k * COL_WAVE + lane];
+        if constexpr (FUSED) {
+            // The sums, here and not after the ranking, so that the 63 words are not held in registers through it (the 4096-pair
+            // instance was 175 registers, two workgroups per CU instead of four).  The words are plain loads, which hipcc counts:
+            // it puts its own vmcnt countdown (62 .. 0) in front of the additions.  As built (COL_SCATTER_KEYS_FIRST = 0) the asm
+            // wait above is vmcnt(0) for keys and values alike, so those waits are already met.  A COL_SCATTER_KEYS_FIRST = 1 build
+            // would NOT keep its overlap here: hipcc does not count the asm loads, and its final vmcnt(0) in front of the last word
+            // also waits for the values before the ranking -- the 63 loads would then have to become asm loads covered by the
+            // explicit wait.  The empty asm statements keep the additions where they stand (volatile asm statements keep their
+            // order; hipcc sinks the additions to their use otherwise).
+            const u32 gb = b / MSD_GROUP, tb = b % MSD_GROUP;
+#pragma unroll
+            for (int g = 0; g < MSD_GROUPS; g++) {
+                asm volatile("" : "+v"(gs[g]));
+                fused_total += gs[g];
+                fused_below += (u32)g < gb ? gs[g] : 0u;
+            }
+#pragma unroll
+            for (int t = 0; t < MSD_GROUP - 1; t++) {
+                asm volatile("" : "+v"(hs[t]));
+                fused_below += (u32)t < tb ? hs[t] : 0u;
+            }
+            asm volatile("" : "+v"(fused_below), "+v"(fused_total));
+        }
     } else {
+        if constexpr (FUSED) {      // the one ragged tile: plain loops, nothing held in registers
+            const u32 gb = b / MSD_GROUP, b0 = b & ~(u32)(MSD_GROUP - 1);
+#pragma unroll 1
+            for (u32 g = 0; g < (u32)MSD_GROUPS; g++) {
+                const u32 v = (fused.gsum + g * RDIG)[tid];
+                fused_total += v;
+                fused_below += g < gb ? v : 0u;
+            }
+#pragma unroll 1
+            for (u32 t = b0; t < b; t++) fused_below += (offsets + (size_t)t * RDIG)[tid];
+            asm volatile("" : "+v"(fused_below), "+v"(fused_total)::"memory");       // (the tile's loads stay below this line)
+        }
 #pragma unroll
         for (int k = 0; k < IT; k++) {
             const u32 li = wbase + k * COL_WAVE;
@@ -420,6 +484,12 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
     } else
     // digit `tid` (threads 0..255): exclusive over waves, then exclusive over digits; fold both into s_cnt
     {
+        if constexpr (FUSED) {
+            u32 all;
+            const u32 bucket_start = block_excl_scan<NT>(fused_total, s_ws, &all);
+            my_offset = bucket_start + fused_below;
+            if (b == 0) fused.starts[tid] = bucket_start;
+        }
         u32 c[NW], tot = 0;
         if (tid < RDIG) {
 #pragma unroll
@@ -1199,6 +1269,40 @@ int col_radix_sort_msd_dev(void *stream, const uint32_t *keys, uint32_t *keys_ou
         k_bucket_sort<8><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, hist, (u32)nb, oversize, n_real_dev);
     else
         k_bucket_sort<16><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, hist, (u32)nb, oversize, n_real_dev);
+    COL_LAUNCH_OK();
+    return COL_OK;
+}
+
+// col_radix_sort_msd_dev for col_collide without the scan launch (k_scatter, FUSED): the start of `scratch` holds the unscanned
+// counts TILE-MAJOR, `fused` (col_radix_msd_fused_bytes()) the group sums -- col_morton_tile(gsum) writes both, into group sums
+// that were zero -- followed by the 256 bucket starts the pass leaves for k_bucket_sort.  Internal (col_common.h).
+size_t col_radix_msd_fused_bytes(void) { return (size_t)(MSD_GROUPS + 1) * RDIG * sizeof(u32); }
+int col_radix_sort_msd_fused(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out,
+                             uint64_t n, void *scratch, uint32_t *oversize, const uint32_t *n_real_dev, uint32_t *fused) {
+    if (n == 0) return COL_OK;
+    if (!scratch || !vals || !vals_out || !fused) return COL_EINVAL;
+    if (n > COL_MSD_MAX_N) return COL_EINVAL;
+    const u32 tile = tile_auto(n, 4, 4);
+    hipStream_t s = col_stream(stream);
+    const size_t nb = col_ceil_div(n, tile);
+    if (nb > (size_t)MSD_GROUP * MSD_GROUPS) return COL_EINVAL;
+    char *p = (char *)scratch;
+    const u32 *counts = (const u32 *)p; p += align256((size_t)RDIG * nb * sizeof(u32));
+    p += align256(col_scan_scratch_bytes((uint64_t)RDIG * nb));
+    u32 *tmp_keys = (u32 *)p;          p += align256((size_t)n * 4);
+    u32 *tmp_vals = (u32 *)p;
+    u32 *starts = fused + MSD_GROUPS * RDIG;
+    const FusedOn f{fused, starts};
+    if (tile == (u32)(NT_SMALL * IT_SMALL))
+        k_scatter<u32, 4, IT_SMALL, NT_SMALL, false, true><<<dim3((unsigned)nb), dim3(NT_SMALL), 0, s>>>(keys, tmp_keys, vals, tmp_vals, n, (u32)nb, BS_SHIFT, counts, DiagOff{}, f);
+    else
+        k_scatter<u32, 4, IT_BIG, NT_MID, false, true><<<dim3((unsigned)nb), dim3(NT_MID), 0, s>>>(keys, tmp_keys, vals, tmp_vals, n, (u32)nb, BS_SHIFT, counts, DiagOff{}, f);
+    COL_LAUNCH_OK();
+    // (one entry per bucket: k_bucket_sort reads offsets[d * nblocks] with nblocks = 1)
+    if (n <= COL_MSD_SMALL_N)
+        k_bucket_sort<8><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, starts, 1u, oversize, n_real_dev);
+    else
+        k_bucket_sort<16><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, starts, 1u, oversize, n_real_dev);
     COL_LAUNCH_OK();
     return COL_OK;
 }

@@ -92,7 +92,10 @@ __device__ __forceinline__ void block_fold(Acc<T, W, OP> &acc, T *out) {
 }
 
 template <typename T, int W, int OP>
-__global__ __launch_bounds__(RT) void k_reduce1(const Row<T, W> *__restrict__ rows, uint64_t n, T *partials) {
+__global__ __launch_bounds__(RT) void k_reduce1(const Row<T, W> *__restrict__ rows, uint64_t n, T *partials,
+                                                 u32 *__restrict__ zero = nullptr, u32 nzero = 0) {
+    // (col_collide: the group sums of the MSD pass, cleared here for the Morton kernel that follows -- no launch of their own)
+    for (u32 z = blockIdx.x * RT + threadIdx.x; z < nzero; z += gridDim.x * RT) zero[z] = 0;
     Acc<T, W, OP> acc;
     acc.init();
     const uint64_t stride = (uint64_t)gridDim.x * RT;
@@ -296,16 +299,22 @@ int list_by_width(void *stream, const void *values, uint64_t n, int width, const
 extern "C" {
 
 int col_minmax4_stage1(void *stream, const void *rows, uint64_t n, int coord_bytes, void *partials, uint32_t *parts) {
+    return col_minmax4_stage1_zero(stream, rows, n, coord_bytes, partials, parts, nullptr, 0);
+}
+
+int col_minmax4_stage1_zero(void *stream, const void *rows, uint64_t n, int coord_bytes, void *partials, uint32_t *parts,
+                            uint32_t *zero, uint32_t nzero) {
+    if (!zero) nzero = 0;
     uint64_t blocks = col_ceil_div(n, (uint64_t)RT * 16);
     if (blocks > COL_MINMAX_PARTS) blocks = COL_MINMAX_PARTS;
     if (blocks == 0) blocks = 1;
     *parts = (uint32_t)blocks;
     if (coord_bytes == 4)
         k_reduce1<float, 4, COL_OP_MINMAX><<<dim3((unsigned)blocks), dim3(RT), 0, col_stream(stream)>>>(
-            (const Row<float, 4> *)rows, n, (float *)partials);
+            (const Row<float, 4> *)rows, n, (float *)partials, zero, nzero);
     else if (coord_bytes == 8)
         k_reduce1<double, 4, COL_OP_MINMAX><<<dim3((unsigned)blocks), dim3(RT), 0, col_stream(stream)>>>(
-            (const Row<double, 4> *)rows, n, (double *)partials);
+            (const Row<double, 4> *)rows, n, (double *)partials, zero, nzero);
     else
         return COL_EINVAL;
     COL_LAUNCH_OK();

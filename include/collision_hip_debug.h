@@ -31,7 +31,9 @@ void col_debug_lbvh(int mode);          /* diagnostics: timing ablations of k_ch
                                          * round-3 code (shuffle scans, branchy Karras probes) for A/Bs, not a diagnostics instance; likewise
                                          * 2048 (float64 with shuffle scans), 8192 (Karras' searches for every node instead of the climb),
                                          * 16384 (24 KB of unused LDS per workgroup: half the resident workgroups); 4096: the traversal's
-                                         * longest-first walk order whatever the scene (tests) */
+                                         * longest-first walk order whatever the scene (tests); 32768: k_group's tables and
+                                         * k_cross's table look-ups at every size, instead of the direct unions up to the MSD size range
+                                         * (tests, A/Bs) */
 void col_debug_leaf_blocks(float k);    /* leaf-block criterion of the fused LBVH build, process-wide: a node of <= 16 leaves is marked when it is at
                                          * most k leaf boxes wide on every axis; default 3, 0 = no marks, a huge k = every small node */
 void col_debug_radix(int mode);         /* diagnostics: 2 = coalesced output, 4 = blockIdx tile order, 8 = dword loads, 32 = phase stamps,
