@@ -129,18 +129,18 @@ _PROTOS = {
 
 # diagnostics entry points (include/collision_hip_debug.h): not part of the drop-in ABI; bound for tools/, bench.py's
 # ablation legs and the tests that force a code path
+_VOID = "void"      # (restype of an entry point that returns nothing)
 _DEBUG_PROTOS = {
     "col_traverse_stats": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int,
                                   C.c_void_p, C.c_int]),
     "col_debug_xcc_census": (None, [C.c_void_p, C.c_void_p, C.c_uint32]),
-    "col_debug_traverse": (C.c_int, [C.c_int]),
-    "col_debug_walk_profile": (C.c_int, [C.c_void_p, C.c_uint32]),
-    "col_debug_lbvh": (C.c_int, [C.c_int]),
-    "col_debug_leaf_blocks": (C.c_int, [C.c_float]),
-    "col_debug_radix": (C.c_int, [C.c_int]),
+    "col_debug_traverse": (None, [C.c_int]),
+    "col_debug_lbvh": (None, [C.c_int]),
+    "col_debug_leaf_blocks": (_VOID, [C.c_float]),
     "col_debug_copy": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]),
-    "col_debug_radix_stamps": (None, [C.c_void_p, C.c_int]),
     "col_debug_radix_tile": (None, [C.c_int]),
+    "col_lbvh_order_forced": (C.c_int, []),
+    "col_radix_tile_override_active": (C.c_int, []),
 }
 
 EXPORTS = tuple(_PROTOS)
@@ -171,9 +171,11 @@ def cdll():
             pass
     lib = C.CDLL(str(LIB_PATH), mode=C.RTLD_GLOBAL)
     for name, (restype, argtypes) in _PROTOS.items():
+        if name in _DEBUG_PROTOS and not hasattr(lib, name):
+            continue        # (COLLISION_AMD_LIB: another build of the same ABI; the diagnostics are not part of it and differ by build)
         fn = getattr(lib, name)
         fn.argtypes = argtypes
-        fn.restype = C.c_int if restype is None else restype
+        fn.restype = C.c_int if restype is None else None if restype is _VOID else restype
     _cdll = lib
     return lib
 

@@ -365,9 +365,8 @@ template <typename T, bool MAX> __device__ __forceinline__ T wave_min_max(T v) {
 }
 
 // STATS: count phase-2 steps for col_traverse_stats (diagnostics); the production instance carries
-// no counters.  VEC: record loads as vector loads at a uniform address (ablation).
-// WALK: 0 = the generic phase-2 loop; 1 = the asm walk with the in-loop leaf-block test (needs 32-bit record offsets);
-// 2 = the asm walk without it (marked nodes are entered through their leaf chain): the A/B reference of col_debug_traverse(128)
+// no counters.
+// WALK: 0 = the generic phase-2 loop; 1 = the asm walk (needs 32-bit record offsets and 64-byte aligned records)
 // GHOST: the queries are not the tree's own leaves but GHOST spheres (multi-GPU halo, csrc/multi.hip): transport records
 // (x, y, z, r, gid) addressed through `order` -- record numbers sorted by the ghosts' Morton codes, so that the 64
 // ghosts of a packet are neighbours in space -- `*count` of them; a packet has no phase 1 and its walk starts at the
@@ -379,11 +378,7 @@ template <> struct GhostSel<true> { typedef GhostArgs T; };
 
 // (amdgpu_num_sgpr(80): above 80 only ONE 16-wave block fits a CU on this platform -- see the SGPR note at the asm walk;
 // what does not fit is spilled to VGPR lanes, of which there are plenty)
-// PROF (diagnostics, col_debug_traverse bit 12): every packet leaves the time of its phases (100 MHz clock) in
-// g_walk_prof[packet] = {phase 1, phase 2, loading its own leaf records, start tick (low word)}
-#define COL_PROF_PACKETS (1u << 18)
-__device__ uint4 g_walk_prof[COL_PROF_PACKETS];
-template <typename T, bool STATS, bool VEC, int WALK, bool GHOST = false, bool PROF = false>
+template <typename T, bool STATS, int WALK, bool GHOST = false>
 __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_traverse(u32 *__restrict__ pairs, u32 *__restrict__ counter, u32 capacity,
                                                   const T *__restrict__ bounds, u32 n_bound, u64 *__restrict__ stats,
                                                   int mode, typename GhostSel<GHOST>::T ghost = {}, const u32 *__restrict__ n_dev = nullptr,
@@ -410,8 +405,8 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
         __syncthreads();
         sink.chunk = &s_chunk;
     }
-    // (timing ablation, mode bit 4: every wave flushes through a counter of its own -- what the walk costs without the
-    // contention of 50 k atomics on ONE address; the pair list is then garbage)
+    // (mode bit 4 has no setter left: every wave flushes through a counter of its own, the pair list is then garbage.  Taking
+    // it and bits 3, 7 and 10 out moved the 2 M step's median by + 1.7 us against a spread of 1.3: EXPERIMENTS.md R6.3)
     if (!STATS && (mode & 16) && stats) sink.counter = reinterpret_cast<u32 *>(stats) + 32u * ((blockIdx.x * TW + w) & 8191u);
     u32 npackets = (n + 63) / 64;
     if constexpr (GHOST) {
@@ -423,7 +418,7 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
     // XCD-aware order: blockIdx % 8 is the XCD, each with its own L2.  Neighbouring packets walk nearly
     // the same nodes, so every XCD takes one contiguous eighth of the packet groups (16 packets = one
     // block's worth) and its blocks stride through it; the records a block misses in the scalar cache
-    // are then mostly in its XCD's L2 already.  (Speed only; mode bit 3 restores the plain order.)
+    // are then mostly in its XCD's L2 already.  (Speed only; mode bit 3, which has no setter left, restores the plain order.)
     const u32 ngroups = (npackets + TW - 1) / TW;
     const u32 xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3, slots = (gridDim.x + 7u - xcd) >> 3;
     const u32 g_lo = (u32)(((u64)ngroups * xcd) >> 3), g_hi = (u32)(((u64)ngroups * (xcd + 1)) >> 3);
@@ -438,8 +433,8 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
     // the next batch, later ones wait for it; end = ~0: the XCD's range is used up).
     __shared__ unsigned long long s_sched;
     // (the workgroup's FIRST batch is the one its place on the XCD names -- no atomic: 64 workgroups asking one counter at the
-    // start of the launch are served one after the other -- and the counter hands out the batches behind those; mode bit 7
-    // draws the first one too: the A/B.  s_use_perm: did this call's k_cross order this XCD's packets (WALK ORDER below)?)
+    // start of the launch are served one after the other -- and the counter hands out the batches behind those; mode bit 7,
+    // which has no setter left, draws the first one too.  s_use_perm: did this call's k_cross order this XCD's packets (WALK ORDER below)?)
     __shared__ u32 s_use_perm;
     __shared__ u32 s_walk_t0[TW], s_ncost[TW];
     __shared__ uint2 s_costbuf[TW][8];        // (packet, ticks) of a wave's last walks: stored eight at a time, see WALK ORDER below
@@ -515,14 +510,12 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
         const bool ordered = !STATS && !GHOST && dyn && walk_order != nullptr && !only1;
         if (ordered && __builtin_amdgcn_readfirstlane((int)s_use_perm)) {
             // (bit 31: one of the XCD's long walks -- the launch ends when the last of them does, so it runs at raised wave priority
-            // among the 7 other walks of its SIMD; mode bit 10 ignores the bit: the A/B)
+            // among the 7 other walks of its SIMD; mode bit 10, which has no setter left, ignores the bit)
             const u32 e = (u32)__builtin_amdgcn_readfirstlane((int)walk_order[(n_bound + 63u) / 64u + packet]);
             packet = e & 0x7FFFFFFFu;
             if ((e >> 31) && !(mode & 1024)) __builtin_amdgcn_s_setprio(3);
         }
         const u32 q0 = packet * 64, q = q0 + lane;
-        u64 prof_t0 = 0, prof_t1 = 0, prof_t2 = 0;
-        if constexpr (PROF) prof_t0 = wall_clock64();
         T lx = (T)INFINITY, ly = lx, lz = lx, hx = -lx, hy = -lx, hz = -lx;      // empty box: overlaps nothing
         u32 qid = 0, qskip = END;
         if constexpr (GHOST) {
@@ -548,10 +541,6 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
             qid = (u32) * reinterpret_cast<const Bits *>(&b.w);
         }
         const int last = GHOST ? 0 : (int)min(63u, n - 1 - q0);        // wave-uniform: last valid lane
-        if constexpr (PROF) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            prof_t1 = wall_clock64();
-        }
         // phase 1: pairs inside the packet.  Exact float tests cost ~30 wave-instructions per pair
         // and almost all of them fail, so pairs are first screened with boxes quantised to 8 bits
         // per axis inside the packet's union box (lo rounded down, hi rounded up: a real overlap
@@ -638,7 +627,6 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
             round(32, true);
         }
 
-        if constexpr (PROF) prof_t2 = wall_clock64();
         // phase 2: everything after the packet's last leaf, one wave-uniform walk of the skip chain: one
         // 32-byte record per step at a wave-uniform address (scalar load), tested against the 64 query boxes.
         //
@@ -657,12 +645,8 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
         // stay inside one asm loop of 7 scalar instructions per step.  0.077 -> 0.069 ms, config 3 0.88 -> 0.80 ms.
         u32 idx = GHOST ? 0u : (u32)__builtin_amdgcn_readlane((int)qskip, last);      // ghosts: from the root
         if ((mode & 2) || only1) idx = END;
-        if constexpr (PROF) if (mode & (2048 | 4096)) {      // profiling instance only (variant bits 24 / 25): the walk with the lower / upper half of the packet's queries
-            const bool keep = (mode & 2048) ? lane < 32u : lane >= 32u;
-            if (!keep) { lx = ly = lz = (T)INFINITY; hx = hy = hz = -(T)INFINITY; }
-        }
         if (ordered && lane == 0) s_walk_t0[w] = (u32)__builtin_amdgcn_s_memtime();      // (in LDS: two scalar registers held across the walk cost it 8-11 %)
-        if constexpr (sizeof(T) == 4 && WALK == 1 && !VEC) {
+        if constexpr (sizeof(T) == 4 && WALK == 1) {
             const char *rows_b = reinterpret_cast<const char *>(rows);
             const u32 buf_lds = (u32)(uintptr_t)(__attribute__((address_space(3))) void *)sink.buf;      // this wave's staging area
             // (the asm walk narrows EXEC with v_cmpx and restores the mask it found on entry -- the full wave here:
@@ -812,7 +796,7 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
                 if (!hits) break;                                           // the chain ended (idx == END, no block pending)
                 sink.emit(hits, qid, pid);                                  // the staging area was full: flush, then stage;
             }                                                               // then on: the rest of the block (bcnt), the skip link (idx)
-        } else if constexpr (sizeof(T) == 8 && WALK == 1 && !VEC) {
+        } else if constexpr (sizeof(T) == 8 && WALK == 1) {
             // The asm walk for float64 records (round 4): a record is 64 bytes -- {min.xyz, skip}{max.xyz, down} as doubles, the
             // links in the low words of the fourth lanes -- fetched by ONE s_load_dwordx16 into s[40:55] at a 32-bit offset
             // (node << 6; arrays below 4 GB), tested with six v_cmpx_*_f64 against the lanes' boxes (SGPR pair against VGPR
@@ -884,75 +868,6 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
                 if (!hits) break;                                           // the chain ended
                 sink.emit(hits, qid, pid);                                  // the staging area was full: flush, then stage; then on
             }
-        } else if constexpr (sizeof(T) == 4 && WALK == 2 && !VEC) {
-            typedef int v8i __attribute__((ext_vector_type(8)));
-            const char *rows_b = reinterpret_cast<const char *>(rows);
-            const u32 buf_lds = (u32)(uintptr_t)(__attribute__((address_space(3))) void *)sink.buf;
-            while (idx != END) {
-                u64 hits, exec0;
-                u32 off, t0, v0, v1;
-                v8i r;
-                asm volatile("s_mov_b64 %[exec0], exec\n\t"
-                             "s_mov_b32 s67, %[idx]\n"
-                             "1:\n\t"
-                             "s_lshl_b32 %[off], s67, 5\n\t"
-                             "s_load_dwordx8 s[64:71], %[base], %[off]\n\t"
-                             "s_waitcnt lgkmcnt(0)\n\t"
-                             "v_cmpx_lt_f32_e32 vcc, s64, %[hx]\n\t"
-                             "v_cmpx_gt_f32_e32 vcc, s68, %[lx]\n\t"
-                             "v_cmpx_lt_f32_e32 vcc, s65, %[hy]\n\t"
-                             "v_cmpx_gt_f32_e32 vcc, s69, %[ly]\n\t"
-                             "v_cmpx_lt_f32_e32 vcc, s66, %[hz]\n\t"
-                             "v_cmpx_gt_f32_e32 vcc, s70, %[lz]\n\t"
-                             "s_cbranch_execnz 2f\n\t"
-                             "s_mov_b64 exec, %[exec0]\n\t"
-                             "s_cmp_lg_u32 s67, -1\n\t"
-                             "s_cbranch_scc1 1b\n\t"
-                             "s_mov_b32 %[idx], -1\n\t"
-                             "s_mov_b64 %[hits], 0\n\t"
-                             "s_branch 4f\n"
-                             "2:\n\t"
-                             "s_cmp_ge_u32 %[off], %[leaf]\n\t"
-                             "s_cbranch_scc1 3f\n\t"
-                             "s_mov_b64 exec, %[exec0]\n\t"
-                             "s_mov_b32 s67, s71\n\t"                      // descend (down link) ...
-                             "s_bitcmp1_b32 s71, 31\n\t"
-                             "s_cbranch_scc0 1b\n\t"
-                             "s_bfe_u32 s67, s71, 0x1b0004\n\t"            // ... or, a leaf block: on through its leaf chain
-                             "s_add_u32 s67, s67, %[leafidx]\n\t"
-                             "s_branch 1b\n"
-                             "3:\n\t"
-                             "s_bcnt1_i32_b64 %[t0], exec\n\t"
-                             "s_add_u32 %[t0], %[cnt], %[t0]\n\t"
-                             "s_cmp_gt_u32 %[t0], %[capw]\n\t"
-                             "s_cbranch_scc1 5f\n\t"
-                             "v_mbcnt_lo_u32_b32 %[v0], exec_lo, 0\n\t"
-                             "v_mbcnt_hi_u32_b32 %[v0], exec_hi, %[v0]\n\t"
-                             "v_add_u32 %[v0], %[cnt], %[v0]\n\t"
-                             "v_lshl_add_u32 %[v0], %[v0], 3, %[buf]\n\t"
-                             "v_mov_b32 %[v1], s71\n\t"
-                             "ds_write2_b32 %[v0], %[qid], %[v1] offset1:1\n\t"
-                             "s_mov_b32 %[cnt], %[t0]\n\t"
-                             "s_mov_b64 exec, %[exec0]\n\t"
-                             "s_cmp_lg_u32 s67, -1\n\t"
-                             "s_cbranch_scc1 1b\n\t"
-                             "s_mov_b32 %[idx], -1\n\t"
-                             "s_mov_b64 %[hits], 0\n\t"
-                             "s_branch 4f\n"
-                             "5:\n\t"
-                             "s_mov_b64 %[hits], exec\n\t"
-                             "s_mov_b64 exec, %[exec0]\n"
-                             "4:"
-                             : [idx] "+s"(idx), [cnt] "+s"(sink.count), [hits] "=s"(hits), [off] "=&s"(off), [t0] "=&s"(t0),
-                               [v0] "=&v"(v0), [v1] "=&v"(v1), [exec0] "=&s"(exec0), "=&{s[64:71]}"(r)
-                             : [base] "s"(rows_b), [leaf] "s"(leaf_start * 32u), [leafidx] "s"(leaf_start), [capw] "s"((u32)CAPW),
-                               [buf] "s"(buf_lds), [qid] "v"(qid), [hx] "v"(hx), [hy] "v"(hy), [hz] "v"(hz), [lx] "v"(lx),
-                               [ly] "v"(ly), [lz] "v"(lz)
-                             : "vcc", "scc", "memory");
-                if (!hits) break;
-                sink.emit(hits, qid, (u32)r[7]);
-                idx = (u32)r[3];
-            }
         } else {
             auto test = [&](const V4 &a, const V4 &b) -> u64 {
                 return __builtin_amdgcn_ballot_w64(hx > a.x) & __builtin_amdgcn_ballot_w64(lx < b.x) &
@@ -960,9 +875,7 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
                        __builtin_amdgcn_ballot_w64(hz > a.z) & __builtin_amdgcn_ballot_w64(lz < b.z);
             };
             while (idx != END) {
-                u32 li = idx;
-                if (VEC) asm volatile("" : "+v"(li));               // vector load at a uniform address
-                const V4 a = rows[2ull * li], b = rows[2ull * li + 1];
+                const V4 a = rows[2ull * idx], b = rows[2ull * idx + 1];
                 const u32 skip = (u32) * reinterpret_cast<const Bits *>(&a.w);
                 const u32 down = (u32) * reinterpret_cast<const Bits *>(&b.w);
                 const u64 hits = test(a, b);
@@ -992,11 +905,6 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
             }
             if (k == 7u && lane < 8) { const uint2 e = s_costbuf[w][lane]; walk_order[e.x] = e.y; }
             __builtin_amdgcn_s_setprio(0);
-        }
-        if constexpr (PROF) {
-            const u64 prof_t3 = wall_clock64();
-            if (lane == 0 && packet < COL_PROF_PACKETS && !only1)
-                g_walk_prof[packet] = make_uint4((u32)(prof_t2 - prof_t1), (u32)(prof_t3 - prof_t2), (u32)(prof_t1 - prof_t0), (u32)prof_t0);
         }
     }
 
@@ -1066,70 +974,28 @@ __global__ __launch_bounds__(TT) __attribute__((amdgpu_num_sgpr(80))) void k_tra
     }
 }
 
-// Lane-per-query variant: every lane walks its own skip chain (12 visits per query on the uniform
-// scene).  Divergent, but it has no intra-wave phase; kept for sparse scenes, selected by
-// col_traverse's `variant` heuristics and for A/B measurements.
-template <typename T>
-__global__ __launch_bounds__(TT) void k_traverse_lane(u32 *__restrict__ pairs, u32 *__restrict__ counter, u32 capacity,
-                                                       const T *__restrict__ bounds, u32 n, int g_skip) {
-    typedef typename BTypes<T>::V4 V4;
-    typedef typename BTypes<T>::Bits Bits;
-    __shared__ uint2 s_buf[TW][CAPW];
-    __shared__ u32 s_cnt[TW];
-    __shared__ u32 s_base;
-    const u32 lane = lane_id(), w = threadIdx.x / 64;
-    const u32 leaf_start = n - 1;
-    const bool marks = n <= COL_LEAF_BLOCK_MAX_N;
-    const V4 *rows = reinterpret_cast<const V4 *>(bounds);
-    PairSink sink = {s_buf[w], 0u, pairs, counter, capacity, lane, nullptr, nullptr};
-    const u32 npackets = (n + 63) / 64;
-    for (u32 packet = blockIdx.x * TW + w; packet < npackets; packet += gridDim.x * TW) {
-        const u32 q = packet * 64 + lane;
-        T lx = (T)INFINITY, ly = lx, lz = lx, hx = -lx, hy = -lx, hz = -lx;
-        u32 qid = 0, idx = END;
-        if (q < n) {
-            const V4 a = rows[2ull * (leaf_start + q)], b = rows[2ull * (leaf_start + q) + 1];
-            lx = a.x; ly = a.y; lz = a.z; hx = b.x; hy = b.y; hz = b.z;
-            idx = (u32) * reinterpret_cast<const Bits *>(&a.w);
-            qid = (u32) * reinterpret_cast<const Bits *>(&b.w);
-        }
-        if (g_skip) idx = END;
-        while (__ballot(idx != END)) {              // wave-uniform loop so that emit() stays convergent
-            bool hit = false;
-            u32 down = 0;
-            if (idx != END) {
-                const V4 a = rows[2ull * idx], b = rows[2ull * idx + 1];
-                const u32 skip = (u32) * reinterpret_cast<const Bits *>(&a.w);
-                down = (u32) * reinterpret_cast<const Bits *>(&b.w);
-                const bool overlap = hx > a.x && lx < b.x && hy > a.y && ly < b.y && hz > a.z && lz < b.z;
-                const bool leaf = idx >= leaf_start;
-                hit = overlap && leaf;
-                idx = (overlap && !leaf) ? descend_link(down, leaf_start, marks) : skip;
-            }
-            const u64 hits = __ballot(hit);
-            if (hits) sink.emit(hits, qid, down);
-        }
-    }
-    if (lane == 0) s_cnt[w] = sink.count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u32 total = 0;
-        for (int i = 0; i < TW; i++) { const u32 c = s_cnt[i]; s_cnt[i] = total; total += c; }
-        s_base = total ? atomicAdd(counter, total) : 0u;
-    }
-    __syncthreads();
-    sink.copy_out(s_base + s_cnt[w], sink.count);
-}
-
-int g_traverse_variant = 0;       // diagnostics switch, see col_debug_traverse
+int g_traverse_variant = 0;       // col_debug_traverse: bit 15 alone
 // from this many spheres on col_collide's traversal takes its work in dynamic order (k_traverse), and up to
 // COL_SPLIT_UNITS_UPTO a packet is two units (its walk, then its phase 1).  Whole path, one box, static / dynamic / dynamic
-// with split units (tools/dyn_ab.py): 0.5 M 0.119 / 0.123 / 0.119 ms, 1 M 0.171-0.177 / 0.172-0.174 / 0.168-0.169,
+// with split units: 0.5 M 0.119 / 0.123 / 0.119 ms, 1 M 0.171-0.177 / 0.172-0.174 / 0.168-0.169,
 // 2 M 0.302-0.312 / 0.292-0.294 / 0.291-0.292, 4 M 0.624-0.631 / 0.590 / 0.604-0.606, 16 M 2.44 / 2.27 / 2.39; config 3
 // (chunked allocation) 0.5 M 0.311 / 0.314 / 0.297, 1 M 0.602-0.609 / 0.585-0.589 / 0.558-0.566, 2 M 1.47 / 1.39 / 1.34
 #define COL_DYNAMIC_PACKETS_FROM 400000u
 #define COL_SPLIT_UNITS_UPTO 3000000u
 
+// the asm walks need 32-bit record offsets (the record array below 4 GB) and 64-byte aligned records: the float32 walk's
+// leaf-block test fetches candidates with 64-byte scalar loads, which may read up to 32 bytes past the last record -- inside
+// the allocation granule of an aligned array, possibly across a mapping boundary of a 32-byte aligned sub-allocation
+// (include/collision_hip.h: alignment of `bounds`); anything else takes the generic loop
+static bool asm_walk_ok(const void *bounds, uint32_t n, size_t coord_bytes) {
+    return (2ull * n - 1) * 8 * coord_bytes < (1ull << 32) && ((uintptr_t)bounds & 63) == 0;
+}
+
+// Packet walk vs a lane-per-query walk, measured on MI355X at 1 M spheres: 0.109 vs 0.120 ms on the uniform scene, 0.78 vs
+// 1.04 ms on a clustered one (11 M pairs).  Halving the resident waves costs +35 %: about a third of the walk is exposed
+// latency of its dependent record loads at the hardware's 8 waves/SIMD, the rest is instruction issue.
+// `stats`: the counting instance (col_traverse_stats).  `sched` (eight zeroed words): the dynamic packet order (k_traverse,
+// mode bit 8), with split units up to COL_SPLIT_UNITS_UPTO and the walk order of `walk_order`.
 template <typename T>
 int launch_traverse(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const void *bounds,
                     uint32_t n, uint64_t *stats, int mode, uint32_t *sched = nullptr, const uint32_t *n_dev = nullptr,
@@ -1140,65 +1006,15 @@ int launch_traverse(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t c
     dim3 g(blocks), t(TT);
     hipStream_t s = col_stream(stream);
     const T *bd = (const T *)bounds;
-    u64 *st = (u64 *)stats;
-    // Measured on MI355X, 1 M spheres (tools/trav_ab.py): packet walk vs lane-per-query 0.109 vs 0.120 ms on
-    // the uniform scene, 0.78 vs 1.04 ms on a clustered one (11 M pairs).  Walking K = 2 / 4 packets per
-    // wave in lock step was slower (0.134 / 0.169 ms) and is gone.  Halving the resident waves (variant
-    // bit 2: 256 blocks, 4 waves/SIMD) costs +35 % (0.102 -> 0.138 ms), i.e. T ~ 66 us + 288 us /
-    // waves-per-SIMD: about a third of the walk is exposed latency of its dependent record loads at the
-    // hardware's 8 waves/SIMD, the rest is instruction issue.  Vector instead of scalar record loads
-    // (variant bit 1): 0.112 ms.
-    if (g_traverse_variant & 4) g = dim3(blocks > 256 ? 256 : blocks);
-    if (g_traverse_variant & 16) mode |= 8;       // plain packet order
-    if (g_traverse_variant & 256) mode |= 1;      // timing ablation: skip phase 1 (pairs inside the packets)
-    if (g_traverse_variant & 512) mode |= 2;      // timing ablation: skip phase 2 (the walk)
-    if (g_traverse_variant & 16777216) mode |= 2048;      // timing experiment: the walk for lanes 0..31 only
-    if (g_traverse_variant & 33554432) mode |= 4096;      // ... for lanes 32..63 only
-    // (diagnostics buffers: one per device, allocated on first use and kept; variant bits 10 and 13 only)
-    constexpr int MAX_DEV = 16;
-    static u64 *spread_dev[MAX_DEV] = {nullptr};   // timing ablation: per-wave flush counters (variant bit 10)
-    static u32 *dyn_sched_dev[MAX_DEV] = {nullptr};
-    int dev = 0;
-    if (g_traverse_variant & (1024 | 8192)) {
-        COL_HIP(hipGetDevice(&dev));
-        if (dev < 0 || dev >= MAX_DEV) return COL_EINVAL;
-    }
-    u64 *&spread = spread_dev[dev];
-    if (g_traverse_variant & 1024) {
-        if (!spread && hipMalloc((void **)&spread, 8192 * 32 * 4) != hipSuccess) return COL_EINVAL;
-        mode |= 16;
-    }
-    // the asm walk needs 32-bit record offsets (the record array below 4 GB); variant bit 6 forces the generic loop
-    // ... and 64-byte aligned records: its leaf-block test fetches candidates with 64-byte scalar loads, which may read up to 32
-    // bytes past the last record -- inside the allocation granule of an aligned array, possibly across a mapping boundary of
-    // a 32-byte aligned sub-allocation (include/collision_hip.h: alignment of `bounds`); anything else takes the generic loop
-    const bool off32 = (2ull * n - 1) * 8 * sizeof(T) < (1ull << 32) && !(g_traverse_variant & 64) && ((uintptr_t)bounds & 63) == 0;
-    // dynamic packet order (k_traverse, mode bit 8): `sched` = eight zeroed words.  Variant bit 13 forces it (with
-    // counters of its own, cleared by a memset), bit 14 forbids it: the A/B switches of tools/walk3_ab.py
-    u32 *&dyn_sched = dyn_sched_dev[dev];
-    if ((g_traverse_variant & 8192) && !sched && !st && !(mode & (32 | 64))) {
-        if (!dyn_sched && hipMalloc((void **)&dyn_sched, 64) != hipSuccess) return COL_EINVAL;
-        COL_HIP(hipMemsetAsync(dyn_sched, 0, 64, s));
-        sched = dyn_sched;
-    }
-    if (sched && !st && !(g_traverse_variant & (16384 | 1 | 2 | 4 | 128 | 1024))) {      // (the other walks are A/B material)
-        mode |= 256;
-        if (g_traverse_variant & 4194304) mode |= 128;      // A/B: the first batch drawn from the counter too
-        if (g_traverse_variant & 8388608) mode |= 1024;     // A/B: long walks at the ordinary priority
-        if ((n <= COL_SPLIT_UNITS_UPTO || (g_traverse_variant & 65536)) && !(g_traverse_variant & 131072)) mode |= 512;      // split units
-        if (off32 && (g_traverse_variant & 4096)) k_traverse<T, false, false, 1, false, true><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (u64 *)sched, mode, NoGhost{}, n_dev, (g_traverse_variant & 2097152) ? nullptr : walk_order);
-        else if (off32) k_traverse<T, false, false, 1><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (u64 *)sched, mode, NoGhost{}, n_dev, (g_traverse_variant & 2097152) ? nullptr : walk_order);
-        else k_traverse<T, false, false, 0><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (u64 *)sched, mode, NoGhost{}, n_dev, (g_traverse_variant & 2097152) ? nullptr : walk_order);
+    if (stats) {
+        k_traverse<T, true, 0><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (u64 *)stats, mode);
         COL_LAUNCH_OK();
         return COL_OK;
     }
-    if ((g_traverse_variant & 255) == 1) k_traverse_lane<T><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, 0);
-    else if (st) k_traverse<T, true, false, 0><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, st, mode);
-    else if (g_traverse_variant & 2) k_traverse<T, false, true, 0><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, st, mode);
-    else if (off32 && (g_traverse_variant & 128)) k_traverse<T, false, false, 2><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, st, mode);
-    else if (off32 && (g_traverse_variant & 4096)) k_traverse<T, false, false, 1, false, true><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, st, mode, NoGhost{}, n_dev);
-    else if (off32) k_traverse<T, false, false, 1><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (g_traverse_variant & 1024) ? spread : st, mode, NoGhost{}, n_dev);
-    else k_traverse<T, false, false, 0><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, st, mode, NoGhost{}, n_dev);
+    if (sched) mode |= n <= COL_SPLIT_UNITS_UPTO ? 256 | 512 : 256;
+    else walk_order = nullptr;
+    if (asm_walk_ok(bounds, n, sizeof(T))) k_traverse<T, false, 1><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (u64 *)sched, mode, NoGhost{}, n_dev, walk_order);
+    else k_traverse<T, false, 0><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (u64 *)sched, mode, NoGhost{}, n_dev, walk_order);
     COL_LAUNCH_OK();
     return COL_OK;
 }
@@ -1322,8 +1138,7 @@ int launch_traverse_chunked(void *stream, uint32_t *pairs, uint32_t *counter, ui
                             uint32_t n, void *scratch, const uint32_t *n_dev = nullptr, uint32_t *walk_order = nullptr,
                             bool hdr_cleared = false) {
     // (dynamic packet order, its counters in the header's pad: always -- a dense scene's packets differ by 5 x in time)
-    const bool split = (n <= COL_SPLIT_UNITS_UPTO || (g_traverse_variant & 65536)) && !(g_traverse_variant & 131072);
-    const int dyn = (g_traverse_variant & 16384) ? 0 : (split ? 256 | 512 : 256) | ((g_traverse_variant & 4194304) ? 128 : 0) | ((g_traverse_variant & 8388608) ? 1024 : 0);
+    const int dyn = n <= COL_SPLIT_UNITS_UPTO ? 256 | 512 : 256;
     const u32 npackets = (n + 63) / 64;
     u32 blocks = (u32)col_ceil_div(npackets, TW);
     if (blocks > 512) blocks = 512;
@@ -1332,13 +1147,12 @@ int launch_traverse_chunked(void *stream, uint32_t *pairs, uint32_t *counter, ui
     const T *bd = (const T *)bounds;
     ChunkHdr *hdr = (ChunkHdr *)scratch;
     if (!hdr_cleared) COL_HIP(hipMemsetAsync(hdr, 0, 64, s));        // (the whole path: the tree build's last kernel has cleared it)
-    k_traverse<T, false, false, 1><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (u64 *)hdr, 32 | dyn, NoGhost{}, n_dev,
-                                                   (dyn & 256) && !(g_traverse_variant & 2097152) ? walk_order : nullptr);
+    k_traverse<T, false, 1><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (u64 *)hdr, 32 | dyn, NoGhost{}, n_dev, walk_order);
     COL_LAUNCH_OK();
     if (capacity) {
         k_pairs_compact<<<dim3(512), dim3(256), 0, s>>>(pairs, hdr, blocks);
         COL_LAUNCH_OK();
-        k_traverse<T, false, false, 1><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (u64 *)hdr, 64, NoGhost{}, n_dev);
+        k_traverse<T, false, 1><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, (u64 *)hdr, 64, NoGhost{}, n_dev);
         COL_LAUNCH_OK();
     }
     return COL_OK;
@@ -1354,9 +1168,8 @@ int launch_ghost(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capa
     dim3 g(blocks), t(TT);
     hipStream_t s = col_stream(stream);
     const T *bd = (const T *)bounds;
-    const bool off32 = (2ull * n - 1) * 8 * sizeof(T) < (1ull << 32) && !(g_traverse_variant & 64) && ((uintptr_t)bounds & 63) == 0;
-    if (off32) k_traverse<T, false, false, 1, true><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, nullptr, 0, ga, n_dev);
-    else k_traverse<T, false, false, 0, true><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, nullptr, 0, ga, n_dev);
+    if (asm_walk_ok(bounds, n, sizeof(T))) k_traverse<T, false, 1, true><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, nullptr, 0, ga, n_dev);
+    else k_traverse<T, false, 0, true><<<g, t, 0, s>>>(pairs, counter, capacity, bd, n, nullptr, 0, ga, n_dev);
     COL_LAUNCH_OK();
     return COL_OK;
 }
@@ -1378,13 +1191,10 @@ extern "C" int col_traverse_ghost_packets(void *stream, uint32_t *pairs, uint32_
 
 extern "C" {
 
-void col_debug_traverse(int variant) { g_traverse_variant = variant; }
-// diagnostics: the per-packet records of the profiling instances (variant bit 12), 4 words per packet: ticks of 10 ns
-// {phase 1, phase 2, loading the packet's own leaf records, start tick}; npackets <= 2^18
-int col_debug_walk_profile(uint32_t *out, uint32_t npackets) {
-    if (npackets > COL_PROF_PACKETS) return COL_EINVAL;
-    COL_HIP(hipDeviceSynchronize());
-    COL_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_walk_prof), 16ull * npackets));
+// 32768: the dynamic packet order at every size (0 = from COL_DYNAMIC_PACKETS_FROM spheres on)
+int col_debug_traverse(int variant) {
+    if (variant & ~32768) return COL_EINVAL;
+    g_traverse_variant = variant;
     return COL_OK;
 }
 
@@ -1454,10 +1264,7 @@ int col_traverse_chunked(void *stream, uint32_t *pairs, uint32_t *counter, uint3
 static int traverse_chunked_dev(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const col_node *nodes,
                                 const void *bounds, uint32_t n, int coord_bytes, void *scratch, const uint32_t *n_dev,
                                 uint32_t *walk_order, bool hdr_cleared) {
-    const bool off32 = (coord_bytes == 4 || coord_bytes == 8) && (2ull * n - 1) * 8 * (unsigned)coord_bytes < (1ull << 32) &&
-                       ((uintptr_t)bounds & 63) == 0;                                                // (see launch_traverse)
-    if (!off32 || !scratch || (g_traverse_variant & ~(16384 | 32768 | 65536 | 131072 | 2097152 | 4194304 | 8388608)))
-    {
+    if ((coord_bytes != 4 && coord_bytes != 8) || !scratch || !asm_walk_ok(bounds, n, (size_t)coord_bytes)) {
         if (n < 2) return COL_OK;
         if (capacity > 0 && !pairs) return COL_EINVAL;
         if (coord_bytes == 4) return launch_traverse<float>(stream, pairs, counter, capacity, bounds, n, nullptr, 0, nullptr, n_dev);

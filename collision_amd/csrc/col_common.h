@@ -33,7 +33,6 @@ extern "C" int col_lbvh_ex(void *stream, const uint32_t *codes, const uint32_t *
                            uint32_t nzero = 8,       // how many words at zero8 (8: the packet counters; 16: the chunked walk's whole header)
                            uint32_t *report_word = nullptr,   // col_radix_bucket_report's word: the report rides in k_chunk's launch (one
                            uint32_t report_n = 0);            // extra workgroup), report_n = length of `codes` with its pads
-extern "C" int col_lbvh_order_forced(void);      // col_debug_lbvh bit 12: the tests' switch for order_mode 1 at every size
 extern "C" int col_radix_sort_msd_dev(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out,
                                       uint64_t n, void *scratch, uint32_t *oversize, const uint32_t *n_real_dev);   // radix.hip
 
@@ -80,7 +79,6 @@ extern "C" int col_traverse_ghost_packets(void *stream, uint32_t *pairs, uint32_
 extern "C" int col_radix_sort_low_passes(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals,
                                          uint32_t *vals_out, uint64_t n, void *scratch, int passes);      // radix.hip
 extern "C" int col_radix_bucket_report(void *stream, const uint32_t *sorted_codes, uint64_t n, uint32_t *word);   // see radix.hip
-extern "C" int col_radix_tile_override_active(void);      // diagnostics: col_debug_radix_tile() is in force
 
 static inline hipStream_t col_stream(void *s) { return (hipStream_t)s; }
 

@@ -221,7 +221,7 @@ template <typename T> __device__ __forceinline__ void links_store(T *bounds, uin
 // LDS has room for it; float64 (25.3 KB, was 31.4) gets six workgroups per CU instead of five.
 //   leaf[4][C]  the leaf's sphere (x, y, z, r), not its box: the box is c -+ r wherever it is read -- the same two IEEE
 //               operations on the same operands as in the leaf's own thread, so the same bits -- and a third less LDS
-//   flags       the searching instances' ready[C + 1] ([C] = 1 for ever: the 'flag' of a child that is a leaf); CLIMB: meet[],
+//   flags       the wide-index instance's ready[C + 1] ([C] = 1 for ever: the 'flag' of a child that is a leaf); CLIMB: meet[],
 //               two 16-bit places per word (a value is a far end + 1 <= 256; the first arrival ORs it into a zero place and
 //               sees zero, the second sees the first's value -- and spoils the place, which nobody reads again)
 //   adj         one signed byte per delta (-1 .. 63)
@@ -378,17 +378,8 @@ __device__ __forceinline__ void wave_suffix_union(Box<double> &b) {
 struct __attribute__((packed, aligned(4))) LeafTail { u32 right_edge, id; };
 struct __attribute__((packed, aligned(4))) InnerTail { u32 right_edge, child_a, child_b; };
 
-// Diagnostics (col_debug_lbvh: timing ablations of k_chunk) live in a separate instance, DIAG = true, with its
-// own kernel argument; the production instance takes no mode argument and carries none of the branches.
-struct ChunkDiagOff {};
-struct ChunkDiagOn { int mode; };
-template <bool DIAG> struct ChunkDiag { typedef ChunkDiagOff T; };
-template <> struct ChunkDiag<true> { typedef ChunkDiagOn T; };
-__device__ __forceinline__ constexpr int chunk_mode(ChunkDiagOff) { return 0; }
-__device__ __forceinline__ int chunk_mode(ChunkDiagOn d) { return d.mode; }
-
 // WALK ORDER (col_common.h), workgroup `ob` of the 8 x COL_ORDER_SLICES that order the packets of the traversal that follows: part of
-// k_chunk's launch (the first workgroups of its grid: done long before the launch is) or, with the searching instances of k_chunk, of
+// k_chunk's launch (the first workgroups of its grid: done long before the launch is) or, with the wide-index instance of k_chunk, of
 // k_cross's (where they were first, and made that launch 11 us instead of 5 at 1 M spheres).  n: this call's number of leaves.
 constexpr u32 COL_ORDER_SLICES = 8;     // workgroups per XCD that order its packets
 constexpr u32 COL_DEAL_UPTO = COL_DEAL_MAX_N / 512;      // packets per XCD up to which a sparse scene's long walks are dealt
@@ -522,16 +513,18 @@ __device__ __forceinline__ void order_packets(u32 ob, u32 n, u32 n_bound, u32 *_
     return;
 }
 
-template <typename T, bool DIAG, typename I, bool DPP_SCAN = false, bool FAST_DELTA = false, bool CLIMB = false>
+// I: int32_t = the production instance (DPP scans, adjacent deltas, the climb); int64_t = the wide-index instance, which
+// serves n >= 2^30 with shuffle scans and Karras' searches for every node (col_debug_lbvh bit 10: at every size, for tests)
+template <typename T, typename I>
 __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, const u32 *__restrict__ ids,
                                              const T *__restrict__ coords, const T *__restrict__ radii,
                                              const T *__restrict__ packed,
                                              col_node *__restrict__ nodes, T *__restrict__ bounds,
                                              u32 *__restrict__ other_end, T *__restrict__ partial, u32 *__restrict__ cross,
                                              T *__restrict__ tab1, u32 n_bound, T block_k, const u32 *__restrict__ n_dev,
-                                             typename ChunkDiag<DIAG>::T diag, u32 *__restrict__ walk_order = nullptr, int order_mode = 0,
+                                             u32 *__restrict__ walk_order = nullptr, int order_mode = 0,
                                              u32 *report_word = nullptr, u32 report_n = 0) {
-    const int dbg = chunk_mode(diag);        // the constant 0 in the production instance
+    constexpr bool DPP_SCAN = sizeof(I) == 4, FAST_DELTA = DPP_SCAN, CLIMB = DPP_SCAN;
     const u32 n = count_of(n_bound, n_dev);  // (device-side count, col_common.h: the grid is sized for the bound)
     typedef typename BT<T>::V4 V4;
     __shared__ ChunkLds<T, CLIMB> lds;
@@ -542,7 +535,7 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
     // windows.  Same bits; whole path, interleaved A/B of two builds on one box: 1 M uniform 0.1706-0.1736 against
     // 0.1744-0.1757 ms, 2 M 0.293-0.296 against 0.298-0.301, 16 M and config 3 unchanged; a clustered scene at 2 M loses
     // 2.5 % (the deep chunks of a cluster all go to one XCD; strips of 16 chunks going round the XCDs avoid that and
-    // gain 0.4 % instead of 1.5 %: not taken).  col_debug_lbvh bit 5 restores chunk = blockIdx.
+    // gain 0.4 % instead of 1.5 %: not taken).
     // (with a device-side count the grid is sized for the bound: the first `nb` blocks -- dealt round-robin over the XCDs like
     // all blocks -- share the real chunks, the others leave; with the bound's chunk count in the formula two of eight XCDs sat idle
     // at a bound of 1.3 n: 70 instead of 51 us)
@@ -562,11 +555,8 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
     const u32 bid = blockIdx.x - nord;
     const u32 nb = n_dev ? (n + (u32)C - 1) / (u32)C : gridDim.x - nord - nrep;
     if (bid >= nb) return;            // (n == 0 included)
-    u32 chunk = bid;
-    if (!(dbg & 32)) {
-        const u32 q = nb / 8, r = nb % 8, x = bid & 7u;
-        chunk = x * q + (x < r ? x : r) + (bid >> 3);
-    }
+    const u32 q = nb / 8, r = nb % 8, x = bid & 7u;
+    const u32 chunk = x * q + (x < r ? x : r) + (bid >> 3);
     const u32 c0 = chunk * C;
     const u32 p = c0 + tid;
     Codes<I, FAST_DELTA> codes = {gcodes, (LdsWord *)s_codes, (I)c0 - HALO, n};
@@ -610,15 +600,11 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
     Box<T> leaf = box_empty<T>();
     if (!valid) id = 0;
     if (valid) {
-        const u32 gid = (dbg & 1) ? p : id;
+        const u32 gid = id;
         V4 c;
         T r;
         if (packed) {                 // (x, y, z, r) rows written by col_morton_ex: one gather per leaf
-            if (dbg & 16) {               // (timing ablation: the gather as a non-temporal load)
-                typedef T vec4 __attribute__((ext_vector_type(4)));
-                const vec4 v = __builtin_nontemporal_load(reinterpret_cast<const vec4 *>(packed) + gid);
-                c.x = v.x; c.y = v.y; c.z = v.z; c.w = v.w;
-            } else c = reinterpret_cast<const V4 *>(packed)[gid];
+            c = reinterpret_cast<const V4 *>(packed)[gid];
             r = c.w;
         } else {
             c = reinterpret_cast<const V4 *>(coords)[gid];
@@ -748,7 +734,8 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
         const u32 child_b = b_leaf ? leaf_start + gamma + 1 : gamma + 1;
         InnerTail tail = {hi, child_a, child_b};
         *reinterpret_cast<InnerTail *>(&nodes[i].right_edge) = tail;
-        if (!(dbg & 2)) { nodes[child_a].parent = i; nodes[child_b].parent = i; }
+        nodes[child_a].parent = i;
+        nodes[child_b].parent = i;
         other_end[i] = j;
         skip = END;
         if (hi + 1 < n) {
@@ -877,13 +864,12 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
         }
         return;
     }
-    if (p >= leaf_start || (dbg & 4)) return;                      // no barrier below this line
+    if (p >= leaf_start) return;                      // no barrier below this line
     u32 j = 0, gamma = 0, skip, child_a;
     search((u32)tid, j, gamma);
     const u32 i = p;
     const u32 lo = min(i, j), hi = max(i, j);
     node_out((u32)tid, j, gamma, skip, child_a);
-    if (dbg & 8) return;
     if (lo >= c0 && hi < c0 + C) {
         // Both children live in this chunk.  Wait (in LDS, workgroup scope) until their boxes are
         // final, merge, publish.  The tree is at most 64 levels deep, so this ends after <= 64
@@ -1141,10 +1127,9 @@ __global__ __launch_bounds__(256) void k_cross(T *__restrict__ bounds, const u32
     if (i != END) cross_node(bounds, other_end, partial, tabs, i, lin);
 }
 
-int g_dbg = 0;         // process-wide diagnostics switch (col_debug_lbvh); see include/collision_hip.h
-// col_debug_lbvh bits that select a production instance or a host-side choice, not the diagnostics instance of k_chunk
-constexpr int DBG_TABLES = 32768;       // k_group + the table look-ups in k_cross at every size (tests, A/Bs)
-constexpr int DBG_PLAIN = 1024 | 2048 | 4096 | 8192 | 16384 | DBG_TABLES;
+// col_debug_lbvh, process-wide: the wide-index k_chunk at every size / the walk order forced / the tables at every size
+constexpr int DBG_WIDE = 1024, DBG_ORDER = 4096, DBG_TABLES = 32768;
+int g_dbg = 0;
 float g_block_k = 3.0f;   // leaf-block density criterion (col_debug_leaf_blocks): node width <= k x leaf width; 0 = no marks
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -1183,35 +1168,17 @@ int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const 
     for (int h = 0; h < 3; h++) tabs.t[h] = scratch + L.tab[h];
     const u32 nchunks = L.count[0];
     bool ordered_by_chunk = false;       // the production k_chunk orders the traversal's packets itself; otherwise k_cross does
-    // mode bit 10 (1024) alone is not a diagnostics mode: it selects the round-3 production instance -- shuffle scans, branchy
-    // delta() -- for A/Bs (tools/lbvh_scan_ab.py)
-    // (bit 11 (2048), likewise: float64 keeps the shuffle scans -- the A/B of the float64 DPP scans)
-    // (bit 12 (4096): the traversal's walk order is used whatever the previous costs look like -- tests)
-    if (g_dbg & ~DBG_PLAIN)          // (bit 14: 24 KB of unused LDS per workgroup -- half the resident workgroups: a timing experiment)
-        k_chunk<T, true, int64_t><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
-                                                                    (T *)tabs.t[0], n, (T)g_block_k, n_dev, ChunkDiagOn{g_dbg & ~DBG_PLAIN});
-    else if (n < (1u << 30) && (g_dbg & 8192))         // (bit 13: Karras' searches for every node -- the A/B of the climb)
-        k_chunk<T, false, int32_t, true, true><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
-                                                                                 (T *)tabs.t[0], n, (T)g_block_k, n_dev, ChunkDiagOff{});
-    else if (n < (1u << 30) && !(g_dbg & 1024) && !((g_dbg & 2048) && sizeof(T) == 8))       // production
-    {
-        k_chunk<T, false, int32_t, true, true, true><<<dim3(nchunks + (walk_order ? 8u * COL_ORDER_SLICES : 0u) + (report_word ? 1u : 0u)), dim3(C), (g_dbg & 16384) ? 24576 : 0, s>>>(
-            codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, n_dev, ChunkDiagOff{}, walk_order, order_mode,
+    if (n < (1u << 30) && !(g_dbg & DBG_WIDE)) {
+        k_chunk<T, int32_t><<<dim3(nchunks + (walk_order ? 8u * COL_ORDER_SLICES : 0u) + (report_word ? 1u : 0u)), dim3(C), 0, s>>>(
+            codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, n_dev, walk_order, order_mode,
             report_word, report_n);
         ordered_by_chunk = true;
         report_word = nullptr;          // done in that launch
-    }
-    else if (n < (1u << 30) && !(g_dbg & 1024))
-        k_chunk<T, false, int32_t, false, true><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
-                                                                                  (T *)tabs.t[0], n, (T)g_block_k, n_dev, ChunkDiagOff{});
-    else if (n < (1u << 30))
-        k_chunk<T, false, int32_t><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
-                                                                     (T *)tabs.t[0], n, (T)g_block_k, n_dev, ChunkDiagOff{});
-    else
-        k_chunk<T, false, int64_t><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
-                                                                     (T *)tabs.t[0], n, (T)g_block_k, n_dev, ChunkDiagOff{});
+    } else
+        k_chunk<T, int64_t><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
+                                                               (T *)tabs.t[0], n, (T)g_block_k, n_dev);
     COL_LAUNCH_OK();
-    if (report_word) {                  // (an instance of k_chunk without the report's workgroup: the report's own launch)
+    if (report_word) {                  // (the wide-index k_chunk has no report workgroup: the report's own launch)
         const int rc = col_radix_bucket_report((void *)s, codes, report_n, report_word);
         if (rc) return rc;
     }
@@ -1245,8 +1212,12 @@ int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const 
 
 extern "C" {
 
-void col_debug_lbvh(int mode) { g_dbg = mode; }
-int col_lbvh_order_forced(void) { return (g_dbg & 4096) ? 1 : 0; }
+int col_debug_lbvh(int mode) {
+    if (mode & ~(DBG_WIDE | DBG_ORDER | DBG_TABLES)) return COL_EINVAL;
+    g_dbg = mode;
+    return COL_OK;
+}
+int col_lbvh_order_forced(void) { return (g_dbg & DBG_ORDER) ? 1 : 0; }
 void col_debug_leaf_blocks(float k) { g_block_k = k; }
 
 size_t col_lbvh_scratch_bytes(uint32_t n, int coord_bytes) { return layout(n, coord_bytes).total + 256; }

@@ -40,16 +40,9 @@ constexpr int BS_SHIFT_REPORT = 22; // == BS_SHIFT below: the MSD plan's bucket 
 //                                whole line and two partial ones instead of two partial ones per run.
 constexpr int IT_BIG = 16, IT_SMALL = 4, IT_HUGE = 32;
 constexpr int NT_BIG = 512, NT_MID = 256, NT_SMALL = 256, NT_HUGE = 512;
-// COL_SCATTER_KEYS_FIRST = 1: k_scatter waits for its keys only and ranks them while the value loads are still in flight.
-// Measured in round 4 (two builds alternating on one box, 3 x 100 launches each, EXPERIMENTS.md): 0.2556 ms per 64 Mi-pair
-// pass against 0.2328 -- like the pass with its ranking taken away (round 3), a workgroup that reaches its store phase
-// sooner makes the pass SLOWER.  Off.
-#ifndef COL_SCATTER_KEYS_FIRST
-#define COL_SCATTER_KEYS_FIRST 0
-#endif
 // tools/radix_tile_sweep.py.  BIG_N: whole (u32, u32) sorts with the 4096 / 8192 tile at 8 M pairs 0.1772 / 0.1736 ms, 12 M
 // 0.2485 / 0.2367, 16 M 0.3352 / 0.3005 (round 3; it was 16 Mi, taken from a sweep over powers of two)
-constexpr uint64_t SMALL_N = 1u << 20, BIG_N_DEFAULT = 8u << 20, HUGE_N = 32u << 20;
+constexpr uint64_t SMALL_N = 1u << 20, BIG_N = 8u << 20, HUGE_N = 32u << 20;
 constexpr int HG = 16;              // max tiles per histogram block (64-byte rows of hist)
 
 template <int B> struct Val;
@@ -60,23 +53,6 @@ struct alignas(16) V32 { uint4 a, b; };
 template <> struct Val<32> { typedef V32 T; };
 
 template <typename K> __device__ __forceinline__ u32 digit_of(K key, int shift) { return (u32)(key >> shift) & (RDIG - 1); }
-
-// Diagnostics live in their own template instances (DIAG = true), selected by col_debug_radix(mode != 0):
-// the production instances take no mode argument and carry none of the branches below.
-// (mode 32: cycles per phase of k_scatter, summed over blocks)
-__device__ unsigned long long g_stamp[8];
-struct DiagOff {};
-struct DiagOn { int mode; };
-template <bool DIAG> struct DiagArg { typedef DiagOff T; };
-template <> struct DiagArg<true> { typedef DiagOn T; };
-__device__ __forceinline__ constexpr int diag_mode(DiagOff) { return 0; }
-__device__ __forceinline__ int diag_mode(DiagOn d) { return d.mode; }
-#define STAMP(slot)                                                              \
-    if (DIAG && (dbg & 32) && threadIdx.x == 0) {                                \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();              \
-        atomicAdd(&g_stamp[slot], t_ - t_prev);                                  \
-        t_prev = t_;                                                             \
-    }
 
 // lanes of this wave whose 8-bit digit equals mine ("match-any").  For every bit the ballot of
 // that bit is XORed with my own bit replicated over the word: the result marks the lanes that
@@ -207,16 +183,7 @@ __global__ __launch_bounds__(RT) __attribute__((amdgpu_num_sgpr(80))) void k_his
     for (u32 t = 0; t < cnt; t++) row[t] = h[t * RDIG + tid];
 }
 
-// ablation helper (col_debug_radix modes 128 / 256)
-template <int SCOPE, typename X> __device__ __forceinline__ void st_scope(X *p, X v) {
-    if constexpr (sizeof(X) == 4) __hip_atomic_store(reinterpret_cast<u32 *>(p), *reinterpret_cast<u32 *>(&v), __ATOMIC_RELAXED, SCOPE);
-    else if constexpr (sizeof(X) == 8) __hip_atomic_store(reinterpret_cast<u64 *>(p), *reinterpret_cast<u64 *>(&v), __ATOMIC_RELAXED, SCOPE);
-    else *p = v;
-}
-
 // ---- scatter ----
-template <bool NARROW> struct CntType { typedef u32 T; };
-template <> struct CntType<true> { typedef uint16_t T; };
 // FUSED (the MSD pass inside col_collide, col_radix_sort_msd_fused below): there is no scan launch in front of the pass.
 // `offsets` then holds the UNSCANNED counts, tile-major (count of digit d in tile b at [b * 256 + d]), and gsum[g * 256 + d] their
 // sums over group g of MSD_GROUP consecutive tiles, both written by col_morton_tile.  Thread d of tile b adds up its offset itself:
@@ -233,14 +200,13 @@ struct FusedOff {};
 struct FusedOn { const u32 *gsum; u32 *starts; };
 template <bool FUSED> struct FusedArg { typedef FusedOff T; };
 template <> struct FusedArg<true> { typedef FusedOn T; };
-template <typename K, int VB, int IT, int NT, bool DIAG, bool FUSED = false>
+template <typename K, int VB, int IT, int NT, bool FUSED = false>
 __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K *__restrict__ keys_out,
                                                 const void *__restrict__ vals_in_, void *__restrict__ vals_out_,
                                                 uint64_t n, u32 nblocks, int shift,
-                                                const u32 *__restrict__ offsets, typename DiagArg<DIAG>::T diag,
+                                                const u32 *__restrict__ offsets,
                                                 typename FusedArg<FUSED>::T fused = {}) {
-    static_assert(!FUSED || (NT == RDIG && !DIAG), "the fused form: one thread per digit, production instance only");
-    const int dbg = diag_mode(diag);        // the constant 0 in the production instance
+    static_assert(!FUSED || NT == RDIG, "the fused form: one thread per digit");
     constexpr int TILE = NT * IT;
     constexpr int NW = NT / COL_WAVE;
     constexpr bool HAS_V = VB > 0;
@@ -248,13 +214,10 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
     typedef typename Val<(VB > 0 ? VB : 4)>::T V;
     __shared__ __attribute__((aligned(16))) K s_keys[TILE];
     __shared__ __attribute__((aligned(16))) V s_vals[V_LDS ? TILE : 1];
-    // (wave, digit) counters: at most 64 * IT items per wave and TILE per block, so 16 bits do when a block has 16 waves --
-    // with 32-bit counters the 1024-thread instance would not fit two blocks into a CU's LDS
-    typedef typename CntType<(NT > 512)>::T CNT;
+    typedef u32 CNT;       // (wave, digit) counters
     __shared__ CNT s_cnt[NW][RDIG];
     __shared__ u32 s_goff[RDIG];
     __shared__ u32 s_ws[NW];
-    __shared__ u32 s_dstart[DIAG ? RDIG : 1];        // (diagnostics, mode 8192)
 
     const V *vals_in = reinterpret_cast<const V *>(vals_in_);
     V *vals_out = reinterpret_cast<V *>(vals_out_);
@@ -264,24 +227,13 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
     // XCD a contiguous range of tiles: the ~64-byte runs of neighbouring tiles then meet in one L2 and
     // leave it as full lines instead of partial-line writes from 8 different L2s.  (Speed only.)
     u32 b = blockIdx.x;
-    if (DIAG && (dbg & (1 << 22)) && nblocks % (8u << ((dbg >> 24) & 7)) == 0) {
-        // (diagnostics, mode 1 << 22: STRIPS of G = 1 << ((mode >> 24) & 7) consecutive tiles go round the XCDs instead of one
-        // contiguous range per XCD: the resident workgroups then cover ONE window of consecutive tiles, i.e. one contiguous
-        // piece of every digit's output region, and only every G-th pair of neighbouring tiles meets in different L2s)
-        const u32 G = 1u << ((dbg >> 24) & 7), x = b % 8, j = b / 8;
-        b = ((j / G) * 8 + x) * G + (j % G);
-    } else if (!(dbg & 4)) {
+    {
         const u32 q = nblocks / 8, r = nblocks % 8, xcd = b % 8;
         b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
     }
     const uint64_t tile_base = (uint64_t)b * TILE;
     const u32 valid = (u32)min((uint64_t)TILE, n - tile_base);
 
-    unsigned long long t_prev = (DIAG && (dbg & 32)) ? __builtin_amdgcn_s_memtime() : 0ull;
-    (void)t_prev;
-    // (diagnostics, wave priorities by phase -- modes 1 << 23: the store phase raised; 1 << 27: the load phase raised;
-    // 1 << 28: the ranking raised; 1 << 29: an s_sleep between the store phase's steps.  EXPERIMENTS.md R4.14)
-    if (DIAG && (dbg & (1 << 27))) __builtin_amdgcn_s_setprio(3);
     // this tile's global offset of digit `tid`: one scattered 4-byte load per thread, issued now so that
     // its latency hides under the loads and the ranking instead of sitting between two barriers
     // (FUSED: the words this thread adds up instead, see above the kernel -- issued at the same point, inside the branches below)
@@ -295,19 +247,16 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
     V val[V_LDS ? IT : 1];
     constexpr int KV = 16 / sizeof(K);                    // keys per 16-byte load
     constexpr int VV = 16 / sizeof(V);
-    constexpr int NVQ = V_LDS ? IT / VV : 0;              // 16-byte value loads per thread
     typedef u32 v4u __attribute__((ext_vector_type(4)));
     v4u vq[V_LDS ? IT / VV : 1];
     V *vstage = s_vals + w * (COL_WAVE * IT);
-    const bool full = valid == (u32)TILE && !(dbg & 8);
+    const bool full = valid == (u32)TILE;
     if (full) {
         // Full tile: 16-byte global loads (lane l takes KV consecutive keys), transposed to the
         // lane-striped order the ranking needs through this wave's own slice of the LDS staging
         // area.  LDS operations of one wave execute in order, so no barrier is needed.
         // All global loads of the tile (keys AND values) are issued before the first wait: one memory
-        // round trip per tile instead of two.  Round 4: the wave then waits for its KEYS only -- vmcnt counts in
-        // issue order, the NVQ value loads were issued after them -- and ranks them while the values are still on
-        // their way; the values are waited for, transposed and taken into registers after the ranking.
+        // round trip per tile instead of two.  The values are transposed and taken into registers after the ranking.
         u32 gs[FUSED ? MSD_GROUPS : 1], hs[FUSED ? MSD_GROUP - 1 : 1];
         if constexpr (FUSED) {
             const u32 b0 = b & ~(u32)(MSD_GROUP - 1);
@@ -324,30 +273,18 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
         // count asm loads, so every destination passes through an explicit vmcnt statement before
         // its first use (cdna_hip_programming.md 5.7, form ii).
         v4u kq[IT / KV];
-        if (dbg & 64) {                          // timing ablation: non-temporal (streaming) loads
 #pragma unroll
-            for (int j = 0; j < IT / KV; j++)
-                asm volatile("global_load_dwordx4 %0, %1, off nt" : "=v"(kq[j]) : "v"(src + j * (COL_WAVE * KV) + lane * KV) : "memory");
-            if (V_LDS) {
+        for (int j = 0; j < IT / KV; j++)
+            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(kq[j]) : "v"(src + j * (COL_WAVE * KV) + lane * KV) : "memory");
+        if (V_LDS) {
 #pragma unroll
-                for (int j = 0; j < IT / VV; j++)
-                    asm volatile("global_load_dwordx4 %0, %1, off nt" : "=v"(vq[j]) : "v"(vsrc + j * (COL_WAVE * VV) + lane * VV) : "memory");
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < IT / KV; j++)
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(kq[j]) : "v"(src + j * (COL_WAVE * KV) + lane * KV) : "memory");
-            if (V_LDS) {
-#pragma unroll
-                for (int j = 0; j < IT / VV; j++)
-                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(vq[j]) : "v"(vsrc + j * (COL_WAVE * VV) + lane * VV) : "memory");
-            }
+            for (int j = 0; j < IT / VV; j++)
+                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(vq[j]) : "v"(vsrc + j * (COL_WAVE * VV) + lane * VV) : "memory");
         }
-        // (NO control flow between an asm load and its wait: with a run-time choice between two waits here hipcc placed
-        // register copies of the load destinations in front of the waits -- it does not know they are in flight -- and the
-        // kernel ranked garbage.  COL_SCATTER_KEYS_FIRST = 0 builds the round-3 behaviour for A/Bs: tools/ab_radix.sh.)
+        // (NO control flow between an asm load and its wait: hipcc then places register copies of the load destinations in
+        // front of the wait -- it does not know they are in flight.  The wait covers keys and values alike.)
 #pragma unroll
-        for (int j = 0; j < IT / KV; j++) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(kq[j]) : "n"(COL_SCATTER_KEYS_FIRST ? NVQ : 0) : "memory");
+        for (int j = 0; j < IT / KV; j++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(kq[j])::"memory");
 #pragma unroll
         for (int j = 0; j < IT / KV; j++)
             *reinterpret_cast<v4u *>(stage + j * (COL_WAVE * KV) + lane * KV) = kq[j];
@@ -357,12 +294,9 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
         if constexpr (FUSED) {
             // The sums, here and not after the ranking, so that the 63 words are not held in registers through it (the 4096-pair
             // instance was 175 registers, two workgroups per CU instead of four).  The words are plain loads, which hipcc counts:
-            // it puts its own vmcnt countdown (62 .. 0) in front of the additions.  As built (COL_SCATTER_KEYS_FIRST = 0) the asm
-            // wait above is vmcnt(0) for keys and values alike, so those waits are already met.  A COL_SCATTER_KEYS_FIRST = 1 build
-            // would NOT keep its overlap here: hipcc does not count the asm loads, and its final vmcnt(0) in front of the last word
-            // also waits for the values before the ranking -- the 63 loads would then have to become asm loads covered by the
-            // explicit wait.  The empty asm statements keep the additions where they stand (volatile asm statements keep their
-            // order; hipcc sinks the additions to their use otherwise).
+            // it puts its own vmcnt countdown (62 .. 0) in front of the additions; the asm wait above is vmcnt(0), so those
+            // waits are already met.  The empty asm statements keep the additions where they stand (volatile asm statements
+            // keep their order; hipcc sinks the additions to their use otherwise).
             const u32 gb = b / MSD_GROUP, tb = b % MSD_GROUP;
 #pragma unroll
             for (int g = 0; g < MSD_GROUPS; g++) {
@@ -418,27 +352,10 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
             }
         }
     }
-    if (DIAG && (dbg & (1 << 27))) __builtin_amdgcn_s_setprio(0);
     __syncthreads();
-    STAMP(0)      // load + transpose
-    if (DIAG && (dbg & (1 << 28))) __builtin_amdgcn_s_setprio(3);
 
-    // (diagnostics, mode 65536: the input IS the pass's tile-sorted image (mode 2 wrote it) -- an element's slot is its
-    // own index, the digit counts come from the offsets table: no match-any, no counters.  Everything else -- loads,
-    // LDS staging, the stores and their addresses -- is the production code: the kernel's ceiling without its ranking.)
-    const bool norank = DIAG && (dbg & 65536);
     // rank inside (wave, digit): wave-private counters, program order keeps them consistent
     u32 pos[IT];
-    // (diagnostics, mode 1 << 21: the rank from ONE returning LDS atomic per item instead of match-any + counter.  Stable
-    // only if the LDS resolves lanes that hit the same address in lane order -- not an architectural promise, so an
-    // experiment: tools/radix_atomrank_ab.py compares its output with the production pass.)
-    const bool atomrank = DIAG && sizeof(CNT) == 4 && (dbg & (1 << 21));
-    if (atomrank) {
-        if constexpr (sizeof(CNT) == 4) {
-#pragma unroll
-            for (int k = 0; k < IT; k++) pos[k] = atomicAdd(reinterpret_cast<u32 *>(&s_cnt[w][digit_of(key[k], shift)]), 1u);
-        }
-    } else if (!norank) {
 #pragma unroll
     for (int k = 0; k < IT; k++) {
         const u32 d = digit_of(key[k], shift);
@@ -450,9 +367,8 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
         if (below == 0) s_cnt[w][d] = (CNT)(prev + (u32)__popcll(peers));
         pos[k] = prev + below;
     }
-    }
     if (V_LDS && full) {
-        // the values: in flight since the top of the kernel, through this wave's slice of the value image
+        // the values: loaded at the top of the kernel, through this wave's slice of the value image
 #pragma unroll
         for (int j = 0; j < IT / VV; j++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(vq[j])::"memory");
 #pragma unroll
@@ -462,26 +378,8 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
 #pragma unroll
         for (int k = 0; k < IT; k++) val[k] = vstage[k * COL_WAVE + lane];
     }
-    if (DIAG && (dbg & (1 << 28))) __builtin_amdgcn_s_setprio(0);
     __syncthreads();
-    STAMP(1)      // ranking
 
-    if (norank) {
-#pragma unroll
-        for (int k = 0; k < IT; k++) pos[k] = wbase + k * COL_WAVE;
-        u32 cnt = 0;
-        if (tid < RDIG) {
-            const uint64_t flat = (uint64_t)tid * nblocks + b;
-            cnt = (flat + 1 < (uint64_t)RDIG * nblocks ? offsets[flat + 1] : (u32)n) - my_offset;
-        }
-        u32 total;
-        const u32 dstart = block_excl_scan<NT>(cnt, s_ws, &total);
-        if (tid < RDIG) {
-            s_goff[tid] = my_offset - dstart;
-            for (int i = 0; i < NW; i++) s_cnt[i][tid] = 0;
-            if (DIAG) s_dstart[tid] = dstart;
-        }
-    } else
     // digit `tid` (threads 0..255): exclusive over waves, then exclusive over digits; fold both into s_cnt
     {
         if constexpr (FUSED) {
@@ -503,11 +401,9 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
             for (int i = 0; i < NW; i++) { s_cnt[i][tid] = (CNT)run; run += c[i]; }
             // global position of tile-sorted slot i with digit d is s_goff[d] + i
             s_goff[tid] = my_offset - dstart;
-            if (DIAG) s_dstart[tid] = dstart;
         }
     }
     __syncthreads();
-    STAMP(2)      // digit scan + offsets
 
 #pragma unroll
     for (int k = 0; k < IT; k++) {
@@ -525,48 +421,22 @@ __global__ __launch_bounds__(NT) void k_scatter(const K *__restrict__ keys_in, K
         }
     }
     __syncthreads();
-    STAMP(3)      // scatter into LDS
 
     // Read back and stream out: consecutive lanes take consecutive tile-sorted slots, i.e. consecutive
     // addresses inside each digit run.  (Measured and not kept: a lane taking 4 consecutive slots and
     // storing them as one 4-byte-aligned dwordx4 -- 8 store instructions per thread instead of 32 -- is
     // 9 % faster with the output forced coalesced and 2-10 % SLOWER on the real runs, even when every
     // store hits L2: misaligned 16-byte stores are split in the address unit.)
-    if (DIAG && (dbg & (1 << 23))) __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int k = 0; k < IT; k++) {
         const u32 i = k * NT + tid;
-        if (DIAG && (dbg & (1 << 29)) && k) __builtin_amdgcn_s_sleep(2);
         if (i < valid) {
             const K kk = s_keys[i];
-            u32 g = s_goff[digit_of(kk, shift)] + i;
-            if (DIAG) {
-                if (dbg & 2) g = (u32)tile_base + i;           // timing ablation: coalesced output
-                if (dbg & 32768) g &= (1u << 20) - 1;          // timing ablation: every store lands in a 4 MiB window (L2)
-                if (dbg & 8192) {      // timing ablation: every (tile, digit) run in a 128-byte cell of its own, digit-major
-                    const u32 d = digit_of(kk, shift);         // (same spatial pattern as the real runs, but whole aligned lines)
-                    g = (u32)(((u64)d * nblocks + b) * 32 + min(i - s_dstart[d], 31u));
-                }
-            }
-            if (DIAG && (dbg & 16384)) {                       // timing ablation: (key, value) pairs interleaved in ONE output
-                if constexpr (V_LDS && sizeof(K) == 4 && VB == 4)      // array of 8 n bytes at keys_out: a digit run is one 256-byte piece
-                    reinterpret_cast<uint2 *>(keys_out)[g] = make_uint2(kk, s_vals[i]);
-            } else if (DIAG && (dbg & 384)) {                  // timing ablations: stores at system (128) / agent (256) scope
-                if (dbg & 128) {
-                    st_scope<__HIP_MEMORY_SCOPE_SYSTEM>(&keys_out[g], kk);
-                    if (V_LDS) st_scope<__HIP_MEMORY_SCOPE_SYSTEM>(&vals_out[g], s_vals[i]);
-                } else {
-                    st_scope<__HIP_MEMORY_SCOPE_AGENT>(&keys_out[g], kk);
-                    if (V_LDS) st_scope<__HIP_MEMORY_SCOPE_AGENT>(&vals_out[g], s_vals[i]);
-                }
-            } else {
-                keys_out[g] = kk;
-                if (V_LDS) vals_out[g] = s_vals[i];
-            }
+            const u32 g = s_goff[digit_of(kk, shift)] + i;
+            keys_out[g] = kk;
+            if (V_LDS) vals_out[g] = s_vals[i];
         }
     }
-    if (dbg & 32) { __builtin_amdgcn_s_waitcnt(0); }
-    STAMP(4)      // read back + global stores (issue only)
 }
 
 
@@ -938,13 +808,9 @@ __global__ __launch_bounds__(COL_WAVE) void k_ref_scatter(const K *keys, K *keys
     }
 }
 
-// Process-wide diagnostics switches (col_debug_radix / col_debug_radix_tile): they change the kernels of
-// EVERY caller in the process and are not synchronised -- set them from one thread, with no sort in flight.
-int g_radix_dbg = 0;
+// Process-wide diagnostics switch (col_debug_radix_tile): it changes the tile class for EVERY caller in the process and is
+// not synchronised -- set it from one thread, with no sort in flight.
 int g_radix_tile_override = 0;      // 0 = automatic, else 1024 / 4096 / 8192 / 16384
-int g_radix_wide_block = 0;         // the 8192-pair tile with 1024 threads x 8 items (experiment, col_debug_radix_tile(8193))
-uint64_t g_big_n = BIG_N_DEFAULT;    // A/B material (col_debug_radix_tile(16 << 20) = the round-2 threshold; buffers sized before a switch do not follow it)
-#define BIG_N g_big_n
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline bool huge_ok(int key_bytes, int val_bytes) { return key_bytes == 4 && val_bytes == 0; }
 inline u32 tile_auto(uint64_t n, int key_bytes, int val_bytes) {
@@ -1000,18 +866,7 @@ int launch_hist(hipStream_t s, const void *keys, uint64_t n, int val_bytes, int 
 template <typename K, int VB, int IT, int NT>
 int launch_scatter_one(hipStream_t s, const K *ki, K *ko, const void *vals, void *vals_out, uint64_t n, u32 nb, int shift,
                        const u32 *offsets) {
-    dim3 grid(nb), block(NT);
-    // the diagnostics instances exist for the profiled combinations only (u32 keys, no / 4-byte values)
-    if constexpr (sizeof(K) == 4 && (VB == 0 || VB == 4)) {
-        if (g_radix_dbg) {
-            // timing ablation: unused dynamic LDS lowers the number of resident blocks per CU (modes 512 / 1024)
-            const size_t dyn = (g_radix_dbg & 1024) ? 18432 : (g_radix_dbg & 512) ? 4608 : 0;
-            k_scatter<K, VB, IT, NT, true><<<grid, block, dyn, s>>>(ki, ko, vals, vals_out, n, nb, shift, offsets, DiagOn{g_radix_dbg});
-            COL_LAUNCH_OK();
-            return COL_OK;
-        }
-    }
-    k_scatter<K, VB, IT, NT, false><<<grid, block, 0, s>>>(ki, ko, vals, vals_out, n, nb, shift, offsets, DiagOff{});
+    k_scatter<K, VB, IT, NT><<<dim3(nb), dim3(NT), 0, s>>>(ki, ko, vals, vals_out, n, nb, shift, offsets);
     COL_LAUNCH_OK();
     return COL_OK;
 }
@@ -1056,9 +911,6 @@ int launch_scatter(hipStream_t s, const void *keys, void *keys_out, const void *
             }
             return COL_OK;
         }
-        // the 8192-pair tile as 1024 threads x 8 items (32 waves per CU instead of 16, same LDS): col_debug_radix_tile(8193)
-        if (g_radix_wide_block && (vb == 0 || vb == 4 || vb == 8))
-            return launch_scatter_it<K, IT_BIG / 2, NT_BIG * 2>(s, keys, keys_out, vals, vals_out, n, vb, shift, offsets);
         return launch_scatter_it<K, IT_BIG, NT_BIG>(s, keys, keys_out, vals, vals_out, n, vb, shift, offsets);
     }
     return COL_EINVAL;
@@ -1170,20 +1022,9 @@ int col_debug_copy(void *stream, const void *in, void *out, uint64_t bytes, int 
     return COL_OK;
 }
 
-void col_debug_radix(int mode) { g_radix_dbg = mode; }
-
 int col_debug_radix_tile(int tile) {
-    if (tile == 8193 || tile == 8194) { g_radix_wide_block = tile == 8193; return COL_OK; }      // (8194: back to 512 x 16)
-    if (tile == (16 << 20) || tile == (8 << 20)) { g_big_n = (uint64_t)tile; return COL_OK; }                    // the 4096 / 8192 threshold (A/B)
     if (tile != 0 && tile != NT_SMALL * IT_SMALL && tile != NT_MID * IT_BIG && tile != NT_BIG * IT_BIG && tile != NT_HUGE * IT_HUGE) return COL_EINVAL;
     g_radix_tile_override = tile;
-    return COL_OK;
-}
-
-int col_debug_radix_stamps(uint64_t *out, int reset) {
-    unsigned long long h[8] = {0};
-    if (out) { COL_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamp), sizeof(h))); for (int i = 0; i < 8; i++) out[i] = h[i]; }
-    if (reset) { unsigned long long z[8] = {0}; COL_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_stamp), z, sizeof(z))); }
     return COL_OK;
 }
 
@@ -1294,9 +1135,9 @@ int col_radix_sort_msd_fused(void *stream, const uint32_t *keys, uint32_t *keys_
     u32 *starts = fused + MSD_GROUPS * RDIG;
     const FusedOn f{fused, starts};
     if (tile == (u32)(NT_SMALL * IT_SMALL))
-        k_scatter<u32, 4, IT_SMALL, NT_SMALL, false, true><<<dim3((unsigned)nb), dim3(NT_SMALL), 0, s>>>(keys, tmp_keys, vals, tmp_vals, n, (u32)nb, BS_SHIFT, counts, DiagOff{}, f);
+        k_scatter<u32, 4, IT_SMALL, NT_SMALL, true><<<dim3((unsigned)nb), dim3(NT_SMALL), 0, s>>>(keys, tmp_keys, vals, tmp_vals, n, (u32)nb, BS_SHIFT, counts, f);
     else
-        k_scatter<u32, 4, IT_BIG, NT_MID, false, true><<<dim3((unsigned)nb), dim3(NT_MID), 0, s>>>(keys, tmp_keys, vals, tmp_vals, n, (u32)nb, BS_SHIFT, counts, DiagOff{}, f);
+        k_scatter<u32, 4, IT_BIG, NT_MID, true><<<dim3((unsigned)nb), dim3(NT_MID), 0, s>>>(keys, tmp_keys, vals, tmp_vals, n, (u32)nb, BS_SHIFT, counts, f);
     COL_LAUNCH_OK();
     // (one entry per bucket: k_bucket_sort reads offsets[d * nblocks] with nblocks = 1)
     if (n <= COL_MSD_SMALL_N)

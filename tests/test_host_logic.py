@@ -45,6 +45,34 @@ def test_library_exports_every_declared_symbol():
     assert lib.col_error_string(-1).decode().startswith("collision_hip")
 
 
+def test_debug_setters_refuse_what_they_do_not_list():
+    """The three col_debug_* setters take the values include/collision_hip_debug.h lists and nothing else: a retired
+    A/B value is COL_EINVAL and leaves the state as it was."""
+    lib = _lib.cdll()
+    try:
+        for v in (0, 32768):
+            assert lib.col_debug_traverse(v) == 0
+        for v in (0, 1024, 4096, 32768, 1024 | 4096 | 32768):
+            assert lib.col_debug_lbvh(v) == 0
+        for v in (0, 1024, 4096, 8192, 16384):
+            assert lib.col_debug_radix_tile(v) == 0
+        assert lib.col_debug_traverse(0) == 0 and lib.col_debug_lbvh(0) == 0 and lib.col_debug_radix_tile(0) == 0
+        assert lib.col_debug_traverse(128) != 0
+        assert lib.col_debug_lbvh(8192) != 0 and lib.col_debug_lbvh(4096 | 8192) != 0
+        assert lib.col_debug_radix_tile(8193) != 0
+        assert lib.col_lbvh_order_forced() == 0
+        assert lib.col_radix_tile_override_active() == 0
+        # ... and a refusal leaves a state that was set where it is
+        assert lib.col_debug_lbvh(4096) == 0 and lib.col_debug_lbvh(2048) != 0 and lib.col_lbvh_order_forced() == 1
+        assert lib.col_debug_radix_tile(4096) == 0 and lib.col_debug_radix_tile(8 << 20) != 0
+        assert lib.col_radix_tile_override_active() == 1 and _lib.call.col_radix_tile(1000, 4, 4) == 4096
+    finally:
+        lib.col_debug_traverse(0)
+        lib.col_debug_lbvh(0)
+        lib.col_debug_radix_tile(0)
+    assert lib.col_lbvh_order_forced() == 0 and lib.col_radix_tile_override_active() == 0
+
+
 def test_scratch_size_queries_are_monotonic():
     c = _lib.call
     assert c.col_scan_scratch_bytes(1) > 0

@@ -82,10 +82,10 @@ for n in 2000000 16000000; do
     python tools/summarize_prof.py pmc $dbs > $S/path${tag}_pmc.json && rm -rf $O/hbm_${n}_*
     echo "n=$n ok"
 done
-# the traversal before / after leaf blocks and chunked allocation (before: no marks, the walk without block code)
+# the traversal before / after leaf blocks and chunked allocation (before: no marks)
 for scene in uniform config3; do
   for tag in before after; do
-    extra=""; [ $tag = before ] && extra="0 128"
+    extra=""; [ $tag = before ] && extra="0"
     plan=auto; [ $scene = config3 ] && plan=lsd
     i=0
     for c in "SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_BUSY_CYCLES" "SQC_DCACHE_REQ SQC_DCACHE_HITS SQC_DCACHE_MISSES"; do

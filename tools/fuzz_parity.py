@@ -31,8 +31,8 @@ def say(msg):
 
 rng = np.random.RandomState(seed)
 if os.environ.get("COLLISION_FUZZ_TRAVERSE"):
-    from collision_amd._lib import cdll
-    cdll().col_debug_traverse(int(os.environ["COLLISION_FUZZ_TRAVERSE"]))
+    from collision_amd._lib import call
+    call.col_debug_traverse(int(os.environ["COLLISION_FUZZ_TRAVERSE"]))      # (raises on a variant the library refuses)
     say("col_debug_traverse(%s)" % os.environ["COLLISION_FUZZ_TRAVERSE"])
 oracle_mod.build()
 ctx = hip.Context()

@@ -4,6 +4,11 @@ started: SALU as large as VALU = per-lane branches the compiler made of a ternar
 
     python tools/kernel_isa_stats.py collision_amd/csrc/lbvh.hip [name filter]      # -> one line per kernel
     python tools/kernel_isa_stats.py collision_amd/csrc/lbvh.hip k_chunk --loops    # + the loops of each kernel
+    python tools/kernel_isa_stats.py collision_amd/csrc/lbvh.hip --dump DIR         # + DIR/<demangled name>.s per kernel
+
+--dump writes each kernel's instructions and descriptor with its .LBB<m>_<n> labels renumbered per kernel, without comments
+and with its own mangled name replaced, so that `diff -r` of the directories of two builds shows exactly the kernels
+whose instructions, register counts or LDS sizes differ.
 """
 import os
 import re
@@ -29,6 +34,9 @@ def main():
     src = os.path.abspath(sys.argv[1])
     want = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith("--") else ""
     loops = "--loops" in sys.argv
+    dump = sys.argv[sys.argv.index("--dump") + 1] if "--dump" in sys.argv else None
+    if dump:
+        os.makedirs(dump, exist_ok=True)
     with tempfile.TemporaryDirectory() as tmp:
         subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(src),
                         "-save-temps", "-c", src, "-o", "x.o"], cwd=tmp, check=True, stderr=subprocess.DEVNULL)
@@ -60,6 +68,15 @@ def main():
         if want and want not in n:
             continue
         v, s, l, p = meta[r[0]]
+        if dump:
+            order = {}
+            body = re.sub(r"(\.L)?BB(\d+_\d+)", lambda mm: (mm.group(1) or "") + "BB_%d" % order.setdefault(mm.group(2), len(order)), r[9])
+            # (comments name IR blocks and mangled lambdas, which move with any edit of the source; the kernel's own mangled
+            # name stands in its descriptor and section lines)
+            body = re.sub(r"[ \t]*;.*", "", body).replace(r[0], "KERNEL")
+            body = "\n".join(l for l in body.splitlines() if l.strip()) + "\n"
+            with open(os.path.join(dump, n.replace("/", "_") + ".s"), "w") as f:
+                f.write(body)
         print("%-72s %6d %6d %6d %5d %5d %6d %5d %4d   %4s %4s %6s %7s" % ((n[:72],) + r[1:9] + (v, s, l, p)))
         if loops:
             lines = r[9].splitlines()

@@ -1,5 +1,6 @@
 """col_lbvh alone on sorted random 30-bit codes (no traversal: safe for experimental builds whose trees are wrong).
-    python tools/lbvh_only.py [n ...]      COLLISION_AMD_LIB selects the build, COLLISION_LBVH_MODE the col_debug_lbvh mode"""
+    python tools/lbvh_only.py [n ...]      COLLISION_AMD_LIB selects the build, COLLISION_LBVH_MODE the col_debug_lbvh mode
+(a mode the library refuses ends the run with HipError)"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -8,7 +9,7 @@ from collision_amd._lib import call, cdll
 import bench
 ctx = hip.Context(); cq = hip.CommandQueue(ctx)
 if os.environ.get("COLLISION_LBVH_MODE"):
-    cdll().col_debug_lbvh(int(os.environ["COLLISION_LBVH_MODE"]))
+    call.col_debug_lbvh(int(os.environ["COLLISION_LBVH_MODE"]))
 for n in [int(a) for a in sys.argv[1:]] or [1000000, 16000000]:
     rng = np.random.default_rng(3)
     codes = np.sort(rng.integers(0, 1 << 30, n, dtype=np.uint32))

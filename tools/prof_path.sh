@@ -1,6 +1,6 @@
 # rocprofv3 kernel stats of the path: bash tools/prof_path.sh "<n> <plan> <scene>" ...   (from the repo root on the GPU box)
-set -o pipefail
-R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; export TMPDIR=/tmp
+set -eu -o pipefail
+R=$(cd "$(dirname "$0")/.." && pwd); O=$R/prof_out; mkdir -p $O; export TMPDIR=/tmp
 for spec in "$@"; do
   set -- $spec
   rm -rf $O/pp

@@ -1,4 +1,5 @@
-"""Traversal time against the leaf-block criterion k (col_debug_leaf_blocks): uniform config 2 and clustered config 3."""
+"""Traversal time against the leaf-block criterion k (col_debug_leaf_blocks): uniform config 2 and clustered config 3.
+    python tools/trav_blocks.py [k ...]      (default: 0 3 0 3; 0 = no marks)"""
 import ctypes, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,9 +15,8 @@ for name, (coords, radii), cap in (("uniform", bench.uniform_scene(n), 1 << 17),
     nb, pb = hip.Buffer(ctx, 4), hip.Buffer(ctx, cap * 8)
     col = Collider(ctx, n, 64, 256)
     col.sort_plan = "lsd" if name == "config3" else "auto"
-    for k, variant in ((3.0, 0), (3.0, 1024), (3.0, 0), (3.0, 1024)):
+    for k in [float(a) for a in sys.argv[1:]] or (0.0, 3.0, 0.0, 3.0):
         lib.col_debug_leaf_blocks(ctypes.c_float(k))
-        lib.col_debug_traverse(variant)
         def step():
             col.get_collisions(cq, cb, rb, nb, pb, cap)
         for _ in range(3): step()
@@ -26,5 +26,5 @@ for name, (coords, radii), cap in (("uniform", bench.uniform_scene(n), 1 << 17),
             call.col_traverse(cq.stream, pb.ptr, nb.ptr, cap, col._nodes_buf.ptr, col._bounds_buf.ptr, n, 4)
         trav(); cq.finish()
         t = bench.time_events(hip, cq, trav, 10)
-        print("%-8s k=%-6g variant %3d whole %.4f ms  traverse %.4f ms  pairs %d" % (name, k, variant, whole, t, int(hip.read_buffer(cq, nb, np.uint32, 1)[0]) ))
-lib.col_debug_leaf_blocks(ctypes.c_float(3.0)); lib.col_debug_traverse(0)
+        print("%-8s k=%-6g whole %.4f ms  traverse %.4f ms  pairs %d" % (name, k, whole, t, int(hip.read_buffer(cq, nb, np.uint32, 1)[0]) ))
+lib.col_debug_leaf_blocks(ctypes.c_float(3.0))
