@@ -83,6 +83,11 @@ class Collider:
         self._lsd_calls_left = 0
         self._retry_after = self.PLAN_RETRY
         self._tried_msd = False
+        # The Node array: nothing on the path reads it (the walk runs on `bounds`), so get_collisions passes no `nodes`
+        # pointer and the array is not allocated -- until somebody reads `_nodes_buf`: from then on ("keep mode") every call
+        # writes it.  (A library from before col_version 101 -- COLLISION_AMD_LIB, an A/B of two builds -- needs the pointer.)
+        self._keep_nodes = call.col_version() < 101
+        self._last_call = None        # (queue, n, sorted codes) of the last call: what a first reader of _nodes_buf gets the records of
 
     # -- sizes -----------------------------------------------------------------
     @property
@@ -101,17 +106,53 @@ class Collider:
         want = {
             "ids0": self.padded_size * 4, "ids1": self.padded_size * 4,
             "codes0": self.padded_size * 4, "codes1": self.padded_size * 4,
-            "nodes": self.n_nodes * Node.itemsize,
             "bounds": self.n_nodes * 2 * 4 * coord_bytes,     # also carries the traversal links
             "scratch": call.col_collide_scratch_bytes(self.size, self.padded_size, coord_bytes),
         }
+        if self._keep_nodes:
+            want["nodes"] = self.n_nodes * Node.itemsize
         for name, nbytes in want.items():
             if name not in self._alloc or self._alloc[name].size != nbytes:
                 self._alloc[name] = hip.Buffer(ctx, nbytes)
         a = self._alloc
         self._ids_bufs = [a["ids0"], a["ids1"]]
         self._codes_bufs = [a["codes0"], a["codes1"]]
-        self._nodes_buf, self._bounds_buf = a["nodes"], a["bounds"]
+        self._bounds_buf = a["bounds"]
+
+    @property
+    def _nodes_ptr(self):
+        """The `nodes` argument of the C calls (after _allocate): NULL until somebody has asked for _nodes_buf."""
+        return self._alloc["nodes"].ptr if self._keep_nodes else None
+
+    @property
+    def _nodes_buf(self):
+        """The reference's Node array (collision.py:66-68).  The first access allocates it, fills it for the last call
+        (_fill_nodes) and switches the collider to keep mode: every later call passes the pointer and the tree build writes
+        the records itself, across resize and re-allocation."""
+        if not self._keep_nodes:
+            self._keep_nodes = True
+            self._allocate()
+            self._fill_nodes()
+        elif "nodes" not in self._alloc or self._alloc["nodes"].size != self.n_nodes * Node.itemsize:
+            self._allocate()
+        return self._alloc["nodes"]
+
+    def _fill_nodes(self):
+        """Node records of the last call, from the sorted codes and ids it left in _codes_bufs[1] / _ids_bufs[1] (the tree's
+        topology depends on nothing else): col_bvh_build without `bounds` writes exactly the fields the fused build writes
+        -- not the root's parent, not a leaf's data[1] -- and leaves the collider's bounds alone.  Enqueued on that call's
+        queue and waited for, so that a reader on any queue sees the records."""
+        if self._last_call is None:
+            return
+        cq, n, codes = self._last_call
+        if codes is not self._codes_bufs[1]:
+            return                                # (resized and re-allocated since: that call's codes are gone)
+        n = n() if callable(n) else n             # (multi.py: an owned count that was still on the device at the call)
+        if not n or 2 * n - 1 > self.n_nodes:
+            return
+        call.col_bvh_build(cq.stream, self._codes_bufs[1].ptr, self._ids_bufs[1].ptr, self._alloc["nodes"].ptr, None, n,
+                           self.program.coord_dtype.itemsize)
+        cq.finish()
 
     @property
     def _flags_buf(self):
@@ -147,11 +188,12 @@ class Collider:
         # counter's content BEFORE a call zeroes it, which is a previous result only on a buffer that had one)
         self._same_counter_calls = self._same_counter_calls + 1 if n_collisions_buf.ptr == self._last_counter else 0
         self._last_counter = n_collisions_buf.ptr
+        self._last_call = (cq, self.size, self._codes_bufs[1])
         call.col_collide_plan(
             cq.stream, coords_buf.ptr, radii_buf.ptr, self.size, self.padded_size,
             self.program.coord_dtype.itemsize,
             self._codes_bufs[0].ptr, self._codes_bufs[1].ptr, self._ids_bufs[0].ptr, self._ids_bufs[1].ptr,
-            self._nodes_buf.ptr, self._bounds_buf.ptr, None, self._alloc["scratch"].ptr,
+            self._nodes_ptr, self._bounds_buf.ptr, None, self._alloc["scratch"].ptr,
             n_collisions_buf.ptr, None if collisions_buf is None else collisions_buf.ptr, n_collisions,
             self._choose_plan(n_collisions), self._plan_word)
         return hip.Event(cq)

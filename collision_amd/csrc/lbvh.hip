@@ -515,7 +515,11 @@ __device__ __forceinline__ void order_packets(u32 ob, u32 n, u32 n_bound, u32 *_
 
 // I: int32_t = the production instance (DPP scans, adjacent deltas, the climb); int64_t = the wide-index instance, which
 // serves n >= 2^30 with shuffle scans and Karras' searches for every node (col_debug_lbvh bit 10: at every size, for tests)
-template <typename T, typename I>
+// NODES = false: the caller passed no `nodes` array (nothing on the collide path reads it: the walk runs on `bounds`, k_cross
+// on other_end[] of the crossing nodes).  The instance has no store into nodes[] and writes other_end[i] for crossing nodes
+// only -- 5 of a thread's 7 global stores and 36 of the 100 bytes per sphere; bounds, partial, cross and the chunk totals are
+// the same bits.  A compile-time parameter: the nodes-writing instances are instruction for instruction what they were.
+template <typename T, typename I, bool NODES = true>
 __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, const u32 *__restrict__ ids,
                                              const T *__restrict__ coords, const T *__restrict__ radii,
                                              const T *__restrict__ packed,
@@ -639,8 +643,10 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
     }
 
     if (valid) {
-        LeafTail tail = {p, id};
-        *reinterpret_cast<LeafTail *>(&nodes[leaf_start + p].right_edge) = tail;
+        if constexpr (NODES) {
+            LeafTail tail = {p, id};
+            *reinterpret_cast<LeafTail *>(&nodes[leaf_start + p].right_edge) = tail;
+        }
         u32 skip_leaf = END;
         if (p + 1 < n) {
             if constexpr (FAST_DELTA && sizeof(I) == 4) {
@@ -725,18 +731,22 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
         gamma = dir > 0 ? (u32)(i + s) : (u32)(i - s - 1);
     };
     // node c0 + t with its other end j and its split: the node record's tail, the children's parent words, the links; returns
-    // the skip link and the left child (collision.cl:104-120)
-    auto node_out = [&](u32 t, u32 j, u32 gamma, u32 &skip, u32 &child_a) {
+    // the skip link and the left child (collision.cl:104-120).  `crossing`: k_cross will ask for the node's other end (without
+    // NODES nobody else does)
+    auto node_out = [&](u32 t, u32 j, u32 gamma, u32 &skip, u32 &child_a, bool crossing) {
         const u32 i = c0 + t;
         const u32 lo = min(i, j), hi = max(i, j);
         const bool a_leaf = lo == gamma, b_leaf = hi == gamma + 1;
         child_a = a_leaf ? leaf_start + gamma : gamma;
         const u32 child_b = b_leaf ? leaf_start + gamma + 1 : gamma + 1;
-        InnerTail tail = {hi, child_a, child_b};
-        *reinterpret_cast<InnerTail *>(&nodes[i].right_edge) = tail;
-        nodes[child_a].parent = i;
-        nodes[child_b].parent = i;
-        other_end[i] = j;
+        if constexpr (NODES) {
+            InnerTail tail = {hi, child_a, child_b};
+            *reinterpret_cast<InnerTail *>(&nodes[i].right_edge) = tail;
+            nodes[child_a].parent = i;
+            nodes[child_b].parent = i;
+        }
+        // (the wide-index instance keeps every word: it has no oe[] to make up for them in a dense chunk, see crossing_out)
+        if (NODES || !CLIMB || crossing) other_end[i] = j;
         skip = END;
         if (hi + 1 < n) {
             if constexpr (FAST_DELTA && sizeof(I) == 4) {
@@ -775,6 +785,15 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
         box_store(partial, i, dir > 0 ? suf : pre);
         const u32 slot = atomicAdd(&lds.ncross, 1u);
         cross[(uint64_t)chunk * CROSS_CAP + (slot < CROSS_CAP - 1 ? slot : CROSS_CAP - 1)] = slot < CROSS_CAP - 1 ? i : CROSS_DENSE;
+        if constexpr (!NODES && CLIMB) {
+            // A dense chunk: k_cross goes through ALL its nodes and tells the crossing ones by other_end[], so the words the
+            // named nodes did not write are due after all.  The one thread that finds the list full writes them from oe[]
+            // (final since the climb's barrier); a chunk in thousands, on clustered scenes only.
+            if (slot == CROSS_CAP - 1)
+#pragma unroll 1
+                for (u32 t = 0; t < (u32)C && c0 + t < leaf_start; t++)
+                    if (lds.oe[t] != (unsigned char)t) other_end[c0 + t] = c0 + lds.oe[t];
+        }
     };
     if constexpr (CLIMB) {
         // A node the climb has named: everything is known.  The others -- three in a hundred: their ranges cross the chunk's boundary --
@@ -792,7 +811,7 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
         u32 skip, child_a;
         if (named) {
             const u32 j = c0 + lds.oe[tid];
-            node_out((u32)tid, j, c0 + lds.split[tid], skip, child_a);
+            node_out((u32)tid, j, c0 + lds.split[tid], skip, child_a, false);
             record_out(p, j, skip, child_a, soa_get(lds.node, tid));
         } else if (inner) crossing_out(p, d_next > d_prev ? 1 : -1);
         const u64 todo = __builtin_amdgcn_ballot_w64(inner && !named);
@@ -858,7 +877,7 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
             const I s = run_end((I)0, len, delta_node);
             const u32 gamma = dir > 0 ? (u32)(i + s) : (u32)(i - s - 1);
             if (on && sub == 0) {
-                node_out(t, j, gamma, skip, child_a);
+                node_out(t, j, gamma, skip, child_a, true);
                 links_store(bounds, (uint64_t)i, skip, child_a);
             }
         }
@@ -869,7 +888,7 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
     search((u32)tid, j, gamma);
     const u32 i = p;
     const u32 lo = min(i, j), hi = max(i, j);
-    node_out((u32)tid, j, gamma, skip, child_a);
+    node_out((u32)tid, j, gamma, skip, child_a, !(lo >= c0 && hi < c0 + C));
     if (lo >= c0 && hi < c0 + C) {
         // Both children live in this chunk.  Wait (in LDS, workgroup scope) until their boxes are
         // final, merge, publish.  The tree is at most 64 levels deep, so this ends after <= 64
@@ -1169,14 +1188,23 @@ int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const 
     const u32 nchunks = L.count[0];
     bool ordered_by_chunk = false;       // the production k_chunk orders the traversal's packets itself; otherwise k_cross does
     if (n < (1u << 30) && !(g_dbg & DBG_WIDE)) {
-        k_chunk<T, int32_t><<<dim3(nchunks + (walk_order ? 8u * COL_ORDER_SLICES : 0u) + (report_word ? 1u : 0u)), dim3(C), 0, s>>>(
-            codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, n_dev, walk_order, order_mode,
-            report_word, report_n);
+        const dim3 grid(nchunks + (walk_order ? 8u * COL_ORDER_SLICES : 0u) + (report_word ? 1u : 0u));
+        if (nodes)
+            k_chunk<T, int32_t><<<grid, dim3(C), 0, s>>>(
+                codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, n_dev, walk_order, order_mode,
+                report_word, report_n);
+        else                            // no Node array asked for: the instance without its stores
+            k_chunk<T, int32_t, false><<<grid, dim3(C), 0, s>>>(
+                codes, ids, coords, radii, packed, nullptr, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, n_dev, walk_order, order_mode,
+                report_word, report_n);
         ordered_by_chunk = true;
         report_word = nullptr;          // done in that launch
-    } else
+    } else if (nodes)
         k_chunk<T, int64_t><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
                                                                (T *)tabs.t[0], n, (T)g_block_k, n_dev);
+    else
+        k_chunk<T, int64_t, false><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nullptr, bounds, other_end, partial, cross,
+                                                                      (T *)tabs.t[0], n, (T)g_block_k, n_dev);
     COL_LAUNCH_OK();
     if (report_word) {                  // (the wide-index k_chunk has no report workgroup: the report's own launch)
         const int rc = col_radix_bucket_report((void *)s, codes, report_n, report_word);

@@ -466,19 +466,24 @@ class HipEngine(ProtocolOps):
                                            % self.OWNED_COUNT_TIMEOUT_S)
         return int(word.value & 0xFFFFFFFF)
 
+    def _owned_count_for_nodes(self):
+        return self.n_owned if self.n_owned is not None else self.owned_count()
+
     # -- local path (main stream)
     def collide(self, rows, gids, n):
         """Single-GPU path on the owned spheres; pairs come out as global ids."""
         s = self.cq.stream
         self.n_owned = n
         c, p = self.collider, self._p
+        # (no `nodes` pointer unless somebody has read c._nodes_buf; a first reader gets this call's records: collision.py)
+        c._last_call = (self.cq, n if n is not None else self._owned_count_for_nodes, c._codes_bufs[1])
         if n is None:                             # the count is on the device (owned2[0]): the rank capacity is the bound
             if not (rows is self.owned_rows and self._have_partials):
                 raise RuntimeError("a device-side owned count needs the repartition's early bounds partials")
             self._have_partials = False
             call.col_collide_plan_dev(s, rows.data_ptr(), p["radii"], self.run_bound, roundUp(self.run_bound, 2 * self.group_size), self.cb,
                                       c._codes_bufs[0].ptr, c._codes_bufs[1].ptr, c._ids_bufs[0].ptr, c._ids_bufs[1].ptr,
-                                      c._nodes_buf.ptr, c._bounds_buf.ptr, None, c._alloc["scratch"].ptr,
+                                      c._nodes_ptr, c._bounds_buf.ptr, None, c._alloc["scratch"].ptr,
                                       p["counter"], p["pairs"], self.pair_capacity, c._choose_plan(self.pair_capacity), c._plan_word,
                                       p["_bounds_partials"], self._bounds_parts.value, p["owned2"])
             call.col_translate_pairs(s, p["pairs"], p["counter"], 0, self.pair_capacity, gids.data_ptr())
@@ -492,7 +497,7 @@ class HipEngine(ProtocolOps):
         self._have_partials = False
         call.col_collide_plan_partials(s, rows.data_ptr(), p["radii"], n, roundUp(n, 2 * self.group_size), self.cb,
                                        c._codes_bufs[0].ptr, c._codes_bufs[1].ptr, c._ids_bufs[0].ptr, c._ids_bufs[1].ptr,
-                                       c._nodes_buf.ptr, c._bounds_buf.ptr, None, c._alloc["scratch"].ptr,
+                                       c._nodes_ptr, c._bounds_buf.ptr, None, c._alloc["scratch"].ptr,
                                        p["counter"], p["pairs"], self.pair_capacity, c._choose_plan(self.pair_capacity), c._plan_word,
                                        partials, self._bounds_parts.value if partials else 0)
         call.col_translate_pairs(s, p["pairs"], p["counter"], 0, self.pair_capacity, gids.data_ptr())

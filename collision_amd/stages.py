@@ -27,7 +27,9 @@ def stage_times(hip_mod, ctx, cq, collider, coords_buf, radii_buf, n_buf, pairs_
     s = cq.stream
     codes0, codes1 = c._codes_bufs
     ids0, ids1 = c._ids_bufs
-    nodes, bounds, flags = c._nodes_buf, c._bounds_buf, c._flags_buf
+    # (a Node array of its own for the reference-shaped build / refit: reading c._nodes_buf would make the collider keep
+    # one from here on, and the whole-path stage below is timed the way a caller runs it)
+    nodes, bounds, flags = hip.Buffer(ctx, c.n_nodes * 16), c._bounds_buf, c._flags_buf
     red_scratch = hip.Buffer(ctx, call.col_reduce_scratch_bytes(0 if cb == 4 else 1, 4))
     rng = hip.Buffer(ctx, 256)
     sort_scratch = hip.Buffer(ctx, call.col_radix_scratch_bytes(p, 4, 4))
@@ -65,7 +67,7 @@ def stage_times(hip_mod, ctx, cq, collider, coords_buf, radii_buf, n_buf, pairs_
     lbvh_scratch = hip.Buffer(ctx, call.col_lbvh_scratch_bytes(n, cb))
 
     def f_lbvh():
-        call.col_lbvh(s, codes1.ptr, ids1.ptr, coords_buf.ptr, radii_buf.ptr, nodes.ptr, bounds.ptr,
+        call.col_lbvh(s, codes1.ptr, ids1.ptr, coords_buf.ptr, radii_buf.ptr, c._nodes_ptr, bounds.ptr,
                       lbvh_scratch.ptr, n, cb)
 
     def f_traverse():

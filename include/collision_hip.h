@@ -210,7 +210,12 @@ int col_traverse_chunked(void *stream, uint32_t *pairs, uint32_t *counter, uint3
 /* Fused production form of the three calls above minus the traversal: Karras topology, leaf and
  * internal AABBs and the traversal links in one pass, with no inter-workgroup hand-off (node
  * boxes are range queries over the sorted leaf boxes; see csrc/lbvh.hip).  Same `nodes` and
- * `bounds` contents as col_bvh_build(bounds != NULL) + col_bvh_refit. */
+ * `bounds` contents as col_bvh_build(bounds != NULL) + col_bvh_refit.
+ * `nodes` may be NULL (col_version() >= 101; so in col_collide, col_collide_plan, _partials and _dev): the Node
+ * array is then neither written nor touched -- the traversal runs on `bounds` alone, so a caller that only wants
+ * the pairs saves 16 B x (2n - 1) of memory and 36 of the 100 bytes per sphere the build writes.  `bounds`, the
+ * sorted codes / ids and the pair list are the same bits either way; col_bvh_build(bounds = NULL) on the sorted
+ * codes / ids gives the same Node records afterwards.  A non-NULL `nodes` is written as before. */
 size_t col_lbvh_scratch_bytes(uint32_t n, int coord_bytes);
 int col_lbvh(void *stream, const uint32_t *codes, const uint32_t *ids, const void *coords,
              const void *radii, col_node *nodes, void *bounds, void *scratch, uint32_t n,
@@ -219,7 +224,8 @@ int col_lbvh(void *stream, const uint32_t *codes, const uint32_t *ids, const voi
 /* ---------------------------------------------------------------- whole path
  * Replaces Collider.get_collisions (collision/collision.py:130-198): the whole
  * enqueue DAG as one call.  codes/ids: two buffers of `padded` uint32 each
- * (sorted result in codes[1]/ids[1], as in the reference); nodes 2n-1;
+ * (sorted result in codes[1]/ids[1], as in the reference); nodes 2n-1
+ * or NULL (see col_lbvh: nothing on this path reads them);
  * bounds (2n-1)*8 scalars; flags 2n-1 uint32; scratch from
  * col_collide_scratch_bytes. */
 size_t col_collide_scratch_bytes(uint32_t n, uint32_t padded, int coord_bytes);

@@ -20,7 +20,8 @@ for n in [int(a) for a in sys.argv[1:]] or [1000000, 2000000, 16000000]:
     col = Collider(ctx, n, 64, 256, coord_dtype=DT)
     scratch = hip.Buffer(ctx, call.col_lbvh_scratch_bytes(n, DT.itemsize))
     def lbvh():
-        call.col_lbvh(cq.stream, col._codes_bufs[1].ptr, col._ids_bufs[1].ptr, cb.ptr, rb.ptr, col._nodes_buf.ptr,
+        # (the collider's own `nodes` argument: NULL with this library, the array with one from before col_version 101)
+        call.col_lbvh(cq.stream, col._codes_bufs[1].ptr, col._ids_bufs[1].ptr, cb.ptr, rb.ptr, col._nodes_ptr,
                       col._bounds_buf.ptr, scratch.ptr, n, DT.itemsize)
     def path():
         col.get_collisions(cq, cb, rb, nb, pb, cap)
