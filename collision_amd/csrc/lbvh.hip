@@ -11,13 +11,16 @@
 // over the leaf boxes, and min/max are exact and idempotent: any grouping gives the reference's
 // bits.  So there is no inter-workgroup hand-off at all:
 //
-//   k_chunk   one block per 256 consecutive sorted leaves: sorted codes staged in an LDS window
-//             (chunk +- 256) for Karras' dependent probes; leaf boxes -> LDS; Karras topology for
-//             internal nodes [c*256, c*256+256); a node whose range stays inside the chunk waits in
-//             LDS (workgroup scope) until both children are final, merges them and publishes its
-//             box; every node is written as one 32-byte record (box + traversal links) per thread.
-//             A node that crosses the chunk boundary stores the half of its range that lies in this
-//             chunk (`partial`: the prefix / suffix unions of the chunk's leaf boxes).
+//   k_chunk   one block per 256 consecutive sorted leaves: leaf boxes -> LDS; Karras topology for
+//             internal nodes [c*256, c*256+256); a node whose range stays inside the chunk is built
+//             bottom-up in LDS from the chunk's adjacent deltas (the climb), merges its children and
+//             publishes its box; every node is written as one 32-byte record (box + traversal links)
+//             per thread.  A node that crosses the chunk boundary stores the half of its range that
+//             lies in this chunk (`partial`: the prefix / suffix unions of the chunk's leaf boxes);
+//             Karras' search for its other end, split and links runs in a search workgroup of the
+//             same launch (a wave per chunk, sorted codes staged in an LDS window chunk +- 256 for
+//             the dependent probes).  (The wide-index instance, n >= 2^30, searches for every node
+//             in the chunk's own workgroup and waits in LDS for the children.)
 //   k_group   (above COL_MSD_MAX_N / 256 chunks only; 1-2 tiny launches) sparse tables over chunk totals,
 //             256 chunks per group, then over group totals, ...
 //   k_cross   the ~1-2 % of nodes that cross chunks: partial[first] U partial[last] U the whole chunks in
@@ -34,6 +37,7 @@
 // internal node has that index) stores its prefix itself.
 #include "col_common.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -513,6 +517,228 @@ __device__ __forceinline__ void order_packets(u32 ob, u32 n, u32 n_bound, u32 *_
     return;
 }
 
+// LDS of the production k_chunk: what a workgroup holds depends on its place in the grid -- a chunk's image, a code window for
+// each of the four chunks a search workgroup serves, or the bucket report's 257 words
+template <typename T> union ProdLds {
+    ChunkLds<T, true> chunk;
+    u32 win[C / COL_WAVE][WIN];
+    u32 report[C + 1];
+};
+template <typename T> __device__ __forceinline__ ChunkLds<T, true> &chunk_lds(ProdLds<T> &u) { return u.chunk; }
+template <typename T> __device__ __forceinline__ ChunkLds<T, false> &chunk_lds(ChunkLds<T, false> &c) { return c; }
+// PLACES.  The production k_chunk's grid behind its order_packets workgroups holds chunk workgroups and search workgroups (SEARCH
+// WAVE below: a wave per chunk, four chunks to a workgroup).  blockIdx % 8 is the XCD, each XCD builds one contiguous run of the
+// chunks, and a chunk's searcher runs on the chunk's XCD: it reads its code window from the same L2.  Four layouts were timed
+// (EXPERIMENTS R8; -DCOL_SEARCH_PLACE=k builds one of them at every size, for two builds alternating on one box):
+//   0  [all chunk workgroups][all search workgroups]   the searchers fill the drain of the last round: slower than no split
+//   1  [all search workgroups][all chunk workgroups]   the fastest step at 1 M spheres and on config 3; at 16 M the searchers are
+//                                                      7.6 rounds of resident waves before the first chunk starts: col_lbvh + 6.7 %
+//   2  groups of 40: [8 search workgroups, one per XCD][32 chunk workgroups] -- the searchers of the group's own 32 chunks
+//   3  groups of 40: [32 chunk workgroups][8 search workgroups]   the fastest from 2 M spheres up (2 and 3 are equal there)
+// Kept: 1 up to SEARCH_FIRST_MAX_CHUNKS chunks -- the searchers are then less than one round of the CUs' wave places --, 3 above.
+constexpr u32 SEARCH_FIRST_MAX_CHUNKS = 1500000 / C;           // between the measured sizes: 1 M (layout 1 wins) and 2 M (layout 3)
+constexpr u32 SEARCH_CHUNKS = C / COL_WAVE;                     // chunks per search workgroup
+constexpr u32 PLACE_CHUNKS = 8u * SEARCH_CHUNKS, PLACE_GROUP = PLACE_CHUNKS + 8u;      // 32 chunk workgroups and their 8 search workgroups
+__host__ __device__ __forceinline__ u32 place_layout(u32 chunks) {
+#ifdef COL_SEARCH_PLACE
+    return COL_SEARCH_PLACE;
+#else
+    return chunks <= SEARCH_FIRST_MAX_CHUNKS ? 1u : 3u;
+#endif
+}
+// number of chunk + search workgroups for `chunks` chunks (a bound, under a device-side count)
+__host__ __device__ __forceinline__ u32 place_blocks(u32 chunks) {
+    if (place_layout(chunks) >= 2u) return PLACE_GROUP * ((chunks + PLACE_CHUNKS - 1u) / PLACE_CHUNKS);
+    // (a multiple of 8 search workgroups, so that every XCD gets the same number wherever in the grid they start)
+    return chunks + 8u * (((chunks + 7u) / 8u + SEARCH_CHUNKS - 1u) / SEARCH_CHUNKS);
+}
+// workgroup v of those: a chunk workgroup (its number `bid` among them; bid % 8 is its XCD) or search workgroup `m` of XCD `xcd`
+struct Place { bool searcher; u32 bid, xcd, m; };
+__device__ __forceinline__ Place place_of(u32 v, u32 chunks) {
+    const u32 layout = place_layout(chunks);
+    Place pl = {false, v, 0u, 0u};
+    if (layout >= 2u) {
+        const u32 grp = v / PLACE_GROUP, within = v % PLACE_GROUP;
+        pl.searcher = layout == 2u ? within < 8u : within >= PLACE_CHUNKS;
+        pl.bid = grp * PLACE_CHUNKS + within - (layout == 2u ? 8u : 0u);
+        pl.xcd = within & 7u;
+        pl.m = grp;
+    } else {
+        const u32 nsearch = place_blocks(chunks) - chunks, sfirst = layout == 1u ? 0u : chunks;
+        pl.searcher = v - sfirst < nsearch;
+        pl.bid = layout == 1u ? v - nsearch : v;
+        // (sfirst need not be a multiple of 8: XCD x's first search workgroup is the first at or behind sfirst with v % 8 == x)
+        const u32 u = v - (sfirst & ~7u);
+        pl.xcd = u & 7u;
+        pl.m = (u >> 3) - (pl.xcd < (sfirst & 7u) ? 1u : 0u);
+    }
+    return pl;
+}
+
+// SEARCH WAVE (round 8).  Karras' search for the nodes of chunk c0 / C whose range crosses the chunk's boundary -- their other end,
+// split, children and skip link are functions of the sorted codes and n alone, final before the launch --, by ONE wave of a search
+// workgroup of k_chunk's grid instead of the chunk's own workgroup, which ends at the stores behind its climb: the probes beyond the
+// code window are dependent round trips to global memory, and a chunk workgroup kept its place on the CU (LDS, four wave slots)
+// while one or two of its waves made them.  Which nodes cross is decided by the chunk's 257 adjacent deltas: node t, with
+// dp = adj[t] = delta(c0 + t - 1, c0 + t) and dn = adj[t + 1], runs forward iff dn > dp and crosses iff every delta between it and
+// the chunk's edge on that side -- adj[t + 1 .. 256] forward, adj[0 .. t] backward -- exceeds min(dn, dp) (-1: no such neighbour):
+// a suffix and a prefix minimum, four places per lane.  These are exactly the nodes the climb leaves unnamed
+// (tests/test_crossing_criterion.py).  Every word has one writer: this wave writes other_end[i], the skip and down words of record
+// i and, with NODES, the node's tail and its children's parent words, for crossing nodes i only; the chunk's workgroup writes none
+// of them.  No barrier, no atomics, nothing read that this launch writes.
+template <typename T, bool NODES>
+__device__ __forceinline__ void search_wave(const u32 *__restrict__ gcodes, col_node *__restrict__ nodes, T *__restrict__ bounds,
+                                            u32 *__restrict__ other_end, u32 n, u32 c0, u32 *win) {
+    typedef int32_t I;
+    const u32 lane = lane_id(), leaf_start = n - 1;
+    Codes<I, true> codes = {gcodes, (LdsWord *)win, (I)c0 - HALO, n};
+    // the code window: every load first, one wait (see k_chunk)
+    u32 wcode[WIN / COL_WAVE];
+#pragma unroll
+    for (int k = 0; k < WIN / COL_WAVE; k++) {
+        const I j = codes.w0 + (I)lane + k * COL_WAVE;
+        const bool in = j >= 0 && j < (I)n;
+        const u32 v = gcodes[in ? j : (I)0];
+        wcode[k] = in ? v : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < WIN / COL_WAVE; k++) win[lane + k * COL_WAVE] = wcode[k];
+    // (LDS instructions of one wave are carried out in order: the compiler only has to keep that order)
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+    auto adj_at = [&](u32 u) -> int {                       // delta(c0 + u - 1, c0 + u), 0 <= u <= C + 1
+        const u32 pos = c0 + u;
+        if (pos < 1u || pos >= n) return -1;
+        return (int)min(ffbh_raw(codes.win[HALO + u - 1u] ^ codes.win[HALO + u]), 32u + ffbh_raw((pos - 1u) ^ pos));
+    };
+    int a[5];                                               // adj[4 * lane + e]
+#pragma unroll
+    for (int e = 0; e < 5; e++) a[e] = adj_at(4u * lane + (u32)e);
+    // exclusive prefix minimum over the lanes' adj[4 l .. 4 l + 3], exclusive suffix minimum over their adj[4 l + 1 .. 4 l + 4]
+    int pre = min(min(a[0], a[1]), min(a[2], a[3])), suf = min(min(a[1], a[2]), min(a[3], a[4]));
+#pragma unroll
+    for (int o = 1; o < COL_WAVE; o <<= 1) {
+        const int up = __shfl_up(pre, o, COL_WAVE), dn = __shfl_down(suf, o, COL_WAVE);
+        if (lane >= (u32)o) pre = min(pre, up);
+        if (lane + (u32)o < (u32)COL_WAVE) suf = min(suf, dn);
+    }
+    pre = __shfl_up(pre, 1, COL_WAVE);
+    suf = __shfl_down(suf, 1, COL_WAVE);
+    if (lane == 0) pre = 0x7FFFFFFF;
+    if (lane == COL_WAVE - 1) suf = 0x7FFFFFFF;
+    u64 todo[4];                                            // todo[e]: lanes whose node 4 * lane + e crosses
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        int before = pre, behind = suf;                    // min adj[0 .. t], min adj[t + 1 .. C]
+        for (int k = 0; k <= e; k++) before = min(before, a[k]);
+        for (int k = e + 1; k < 5; k++) behind = min(behind, a[k]);
+        const int dp = a[e], dn = a[e + 1];
+        const bool inner = c0 + 4u * lane + (u32)e < leaf_start;
+        todo[e] = __builtin_amdgcn_ballot_w64(inner && (dn > dp ? behind > dp : before > dn));
+    }
+    const u32 cnt = (u32)(__builtin_popcountll(todo[0]) + __builtin_popcountll(todo[1]) + __builtin_popcountll(todo[2]) +
+                          __builtin_popcountll(todo[3]));
+    if (cnt == 0) return;
+    // A wave shares its lanes among its nodes -- 64, 32, 16 or 8 lanes per node -- and every step of the three searches (each looks
+    // for the end of a run of "yes": delta(i, i + dir * x) > threshold is monotone in x) asks that many places at once: the powers
+    // of two, then equal parts of what is left.  A fifth of the round trips of a search per lane, ~35 instructions per step for the
+    // whole wave.
+    const u32 lpn_log = cnt <= 1 ? 6u : cnt <= 2 ? 5u : cnt <= 4 ? 4u : 3u, lpn = 1u << lpn_log, groups = 64u >> lpn_log;
+    const u32 g = lane >> lpn_log, sub = lane & (lpn - 1u);
+    auto group_count = [&](bool yes) -> I {                 // how many lanes of my group say yes
+        u64 m = __builtin_amdgcn_ballot_w64(yes) >> (g << lpn_log);
+        if (lpn < 64u) m &= (1ull << lpn) - 1ull;
+        return (I)__builtin_popcountll(m);
+    };
+    for (u32 base = 0; base < cnt; base += groups) {
+        const bool on = base + g < cnt;                      // my group has a node this round
+        // node number base + g of the wave's list: todo[0]'s lanes, then todo[1]'s, ...
+        u32 e_sel = 0, skip_bits = base + g;
+        u64 m = todo[0];
+#pragma unroll
+        for (u32 e = 0; e < 3; e++) {
+            const u32 c = (u32)__builtin_popcountll(todo[e]);
+            if (on && e_sel == e && skip_bits >= c) { skip_bits -= c; e_sel = e + 1; m = todo[e + 1]; }
+        }
+        for (u32 b = 0; b < skip_bits && on; b++) m &= m - 1ull;
+        const u32 t = on ? 4u * (u32)__builtin_ctzll(m) + e_sel : lane;
+        const u32 i = c0 + t, ci = codes.win[HALO + t];
+        const int dn = adj_at(t + 1u), dp = adj_at(t);       // delta(i, i + 1), delta(i - 1, i)
+        const int dir = dn > dp ? 1 : -1, delta_min = min(dn, dp);
+        // is place x (0 = none) in the run?  one load per lane; LDS if every lane's place is in the window
+        auto yes_at = [&](I x, int thr) -> bool {
+            const I jk = (I)i + dir * x;
+            const bool inb = on && x > 0 && (u32)jk < n;
+            const u32 o = (u32)(jk - codes.w0);
+            const bool inwin = o < (u32)WIN;
+            u32 cj;
+            if (__builtin_amdgcn_ballot_w64(inb && !inwin) == 0) cj = codes.win[inwin ? o : 0u];
+            else cj = inb ? (inwin ? codes.win[o] : gcodes[jk]) : 0u;
+            const u32 d = min(ffbh_raw(ci ^ cj), 32u + ffbh_raw(i ^ (u32)jk));
+            return inb && (int)d > thr;
+        };
+        // the first power of two that is not in the range any more
+        I hi = 2;
+        {
+            bool more = on;
+            int e0 = 1;
+            while (__builtin_amdgcn_ballot_w64(more)) {
+                const int e = e0 + (int)sub;
+                const I x = (more && e < 31 && (1u << e) <= n) ? (I)(1u << e) : (I)0;
+                const I yes = group_count(yes_at(x, delta_min));
+                if (more) {
+                    hi = (I)(1u << (e0 + yes));
+                    more = yes == (I)lpn && e0 + (int)lpn < 31;
+                    e0 += (int)lpn;
+                }
+            }
+        }
+        // the end of a run of yes between lo (in) and hi (out)
+        auto run_end = [&](I lo, I hi, int thr) -> I {
+            while (__builtin_amdgcn_ballot_w64(on && hi - lo > 1)) {
+                const bool act = on && hi - lo > 1;
+                const I step = (hi - lo + (I)lpn) / ((I)lpn + 1);
+                const I x = lo + ((I)sub + 1) * step;
+                const I yes = group_count(yes_at(act && x < hi ? x : (I)0, thr));
+                if (act) { lo += yes * step; hi = min(hi, lo + step); }
+            }
+            return lo;
+        };
+        const I len = run_end(hi / 2, hi, delta_min);
+        const u32 j = (u32)((I)i + dir * len);
+        const int delta_node = delta(codes, i, ci, (I)j);
+        const I s = run_end((I)0, len, delta_node);
+        const u32 gamma = dir > 0 ? (u32)(i + s) : (u32)(i - s - 1);
+        if (on && sub == 0) {
+            // the node record's tail, the children's parent words, the links (collision.cl:104-120)
+            const u32 lo = min(i, j), top = max(i, j);
+            const bool a_leaf = lo == gamma, b_leaf = top == gamma + 1;
+            const u32 child_a = a_leaf ? leaf_start + gamma : gamma;
+            const u32 child_b = b_leaf ? leaf_start + gamma + 1 : gamma + 1;
+            if constexpr (NODES) {
+                InnerTail tail = {top, child_a, child_b};
+                *reinterpret_cast<InnerTail *>(&nodes[i].right_edge) = tail;
+                nodes[child_a].parent = i;
+                nodes[child_b].parent = i;
+            }
+            other_end[i] = j;
+            u32 skip = END;
+            if (top + 1 < n) {
+                const u32 k = top + 1;
+                if (k + 1 >= n) skip = (n - 1) + k;
+                else {
+                    // is the right child that starts at leaf k an internal node: its three codes in ONE round trip
+                    const u32 ck = codes.at((I)k), cm = codes.at((I)k - 1), cp = codes.at((I)k + 1);
+                    const u32 d_fwd = min(ffbh_raw(ck ^ cp), 32u + ffbh_raw(k ^ (k + 1u))), d_bwd = min(ffbh_raw(ck ^ cm), 32u + ffbh_raw(k ^ (k - 1u)));
+                    skip = d_fwd > d_bwd ? k : (n - 1) + k;
+                }
+            }
+            links_store(bounds, (uint64_t)i, skip, child_a);
+        }
+    }
+}
+
 // I: int32_t = the production instance (DPP scans, adjacent deltas, the climb); int64_t = the wide-index instance, which
 // serves n >= 2^30 with shuffle scans and Karras' searches for every node (col_debug_lbvh bit 10: at every size, for tests)
 // NODES = false: the caller passed no `nodes` array (nothing on the collide path reads it: the walk runs on `bounds`, k_cross
@@ -531,8 +757,12 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
     constexpr bool DPP_SCAN = sizeof(I) == 4, FAST_DELTA = DPP_SCAN, CLIMB = DPP_SCAN;
     const u32 n = count_of(n_bound, n_dev);  // (device-side count, col_common.h: the grid is sized for the bound)
     typedef typename BT<T>::V4 V4;
-    __shared__ ChunkLds<T, CLIMB> lds;
-    __shared__ u32 s_codes[WIN];
+    // (CLIMB: a chunk workgroup keeps no code window -- what it reads of the codes are its own 256, one before and two behind)
+    __shared__ std::conditional_t<CLIMB, ProdLds<T>, ChunkLds<T, false>> lds_mem;
+    __shared__ u32 s_codes_mem[CLIMB ? 1 : WIN];
+    ChunkLds<T, CLIMB> &lds = chunk_lds(lds_mem);
+    u32 *s_codes;
+    if constexpr (CLIMB) s_codes = lds_mem.report; else s_codes = s_codes_mem;
     const int tid = threadIdx.x, lane = tid & (COL_WAVE - 1), w = tid / COL_WAVE;
     // XCD-aware order: blockIdx % 8 is the XCD (each with its own L2).  Every XCD builds one contiguous run of chunks -- the
     // same eighth of the sorted leaves whose packets it walks in k_traverse, and neighbouring chunks read overlapping code
@@ -556,8 +786,20 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
         col_bucket_report_block(gcodes, report_n, report_word, s_codes);
         return;
     }
-    const u32 bid = blockIdx.x - nord;
-    const u32 nb = n_dev ? (n + (u32)C - 1) / (u32)C : gridDim.x - nord - nrep;
+    // (CLIMB: chunk workgroups and search workgroups share the grid -- PLACES above --, both sized for the bound and, under a
+    // device-side count, clamped the same way: the searchers of chunks at or beyond the real count leave)
+    const u32 bound_chunks = (n_bound + (u32)C - 1) / (u32)C;
+    const Place pl = CLIMB ? place_of(blockIdx.x - nord, bound_chunks) : Place{false, blockIdx.x, 0u, 0u};
+    const u32 bid = CLIMB ? pl.bid : blockIdx.x - nord;
+    const u32 nb = n_dev ? (n + (u32)C - 1) / (u32)C : CLIMB ? bound_chunks : gridDim.x - nord - nrep;
+    if constexpr (CLIMB) {
+        if (pl.searcher) {
+            const u32 k = pl.m * SEARCH_CHUNKS + (u32)w, qs = nb / 8, rs = nb % 8, xs = pl.xcd;
+            if (k >= qs + (xs < rs ? 1u : 0u)) return;   // (n == 0 included)
+            search_wave<T, NODES>(gcodes, nodes, bounds, other_end, n, (xs * qs + (xs < rs ? xs : rs) + k) * (u32)C, lds_mem.win[w]);
+            return;
+        }
+    }
     if (bid >= nb) return;            // (n == 0 included)
     const u32 q = nb / 8, r = nb % 8, x = bid & 7u;
     const u32 chunk = x * q + (x < r ? x : r) + (bid >> 3);
@@ -569,9 +811,11 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
     // addresses so that none sits behind a branch -- and ONE wait.  As a loop with the LDS store inside, hipcc waited for
     // each window load before it issued the next: with the id and the row gather five dependent round trips per block,
     // now two.
+    // (CLIMB: no window -- the leaf's own code alone, with its two neighbours below: three loads instead of five and no 3 KB of
+    // LDS; the searches that probed the window run in the search workgroups)
     u32 wcode[WIN / C];
 #pragma unroll
-    for (int k = 0; k < WIN / C; k++) {
+    for (int k = CLIMB ? HALO / C : 0; k < (CLIMB ? HALO / C + 1 : WIN / C); k++) {
         const I j = codes.w0 + tid + k * C;
         const bool in = j >= 0 && j < (I)n;
         const u32 v = gcodes[in ? j : (I)0];
@@ -591,10 +835,18 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
         if (has_next) d_next = (int)min(ffbh_raw(cme ^ cnext), 32u + ffbh_raw(p ^ (p + 1u)));
         lds.adj[1 + tid] = (signed char)d_next;
         if (tid == 0) lds.adj[0] = (signed char)d_prev;
+        // adj[C + 1] = delta(c0 + C, c0 + C + 1): with it "is the right child that starts behind the chunk's last leaf an internal
+        // node" -- the skip link of that leaf and of a node that ends there -- is adj[C + 1] > adj[C] like everywhere else in the
+        // chunk (it was three codes from global memory behind the climb).  One more load, the same address in every lane.
+        const u32 k2 = c0 + (u32)C + 1u;
+        const u32 c2 = gcodes[k2 < n ? k2 : 0u];
+        if (tid == C - 1) lds.adj[C + 1] = k2 < n ? (signed char)min(ffbh_raw(cnext ^ c2), 32u + ffbh_raw((k2 - 1u) ^ k2)) : (signed char)-1;
     }
     if constexpr (CLIMB) { if (tid < C / 2) lds.flags[tid] = 0; lds.oe[tid] = (unsigned char)tid; }
+    if constexpr (!CLIMB) {
 #pragma unroll
-    for (int k = 0; k < WIN / C; k++) s_codes[tid + k * C] = wcode[k];
+        for (int k = 0; k < WIN / C; k++) s_codes[tid + k * C] = wcode[k];
+    }
     if constexpr (!CLIMB) lds.flags[tid] = 0;
     if (tid < (int)CROSS_CAP) cross[(uint64_t)chunk * CROSS_CAP + tid] = END;       // (complete before the barrier below: the fence of __syncthreads)
     if (tid == 0) { lds.ncross = 0; if constexpr (!CLIMB) lds.flags[C] = 1u; }
@@ -652,8 +904,7 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
             if constexpr (FAST_DELTA && sizeof(I) == 4) {
                 const u32 k = p + 1;
                 if (k + 1 >= n) skip_leaf = (n - 1) + k;
-                else if (tid + 1 < C) skip_leaf = lds.adj[tid + 2] > d_next ? k : (n - 1) + k;
-                else skip_leaf = right_child_at(codes, k);            // (the chunk's last leaf: adj[k] belongs to the next chunk)
+                else skip_leaf = lds.adj[tid + 2] > d_next ? k : (n - 1) + k;       // (the chunk's last leaf: adj[C + 1])
             } else skip_leaf = right_child_at(codes, p + 1);
         }
         record_store(bounds, (uint64_t)leaf_start + p, leaf, skip_leaf, id);
@@ -752,13 +1003,8 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
             if constexpr (FAST_DELTA && sizeof(I) == 4) {
                 const u32 k = hi + 1;
                 if (k + 1 >= n) skip = (n - 1) + k;
-                else if (hi >= c0 && k < c0 + (u32)C) skip = lds.adj[k - c0 + 1] > lds.adj[hi - c0 + 1] ? k : (n - 1) + k;
-                else {
-                    // (outside the chunk: the three codes in ONE round trip -- right_child_at's code read and two probes are three)
-                    const u32 ck = gcodes[k], cm = gcodes[k - 1u], cp = gcodes[k + 1u];
-                    const u32 d_fwd = min(ffbh_raw(ck ^ cp), 32u + ffbh_raw(k ^ (k + 1u))), d_bwd = min(ffbh_raw(ck ^ cm), 32u + ffbh_raw(k ^ (k - 1u)));
-                    skip = d_fwd > d_bwd ? k : (n - 1) + k;
-                }
+                // (a named node's range lies in the chunk: c0 <= hi < c0 + C, and behind its last leaf adj[C + 1] answers)
+                else skip = lds.adj[k - c0 + 1] > lds.adj[hi - c0 + 1] ? k : (n - 1) + k;
             } else skip = right_child_at(codes, hi + 1);
         }
     };
@@ -796,16 +1042,14 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
         }
     };
     if constexpr (CLIMB) {
-        // A node the climb has named: everything is known.  The others -- three in a hundred: their ranges cross the chunk's boundary --
-        // leave their half box themselves (the direction is in adj[]); what they still need is Karras' search, and what that costs
-        // is the ROUND TRIPS of the probes that leave the code window: a workgroup held its place on the CU while one lane asked
-        // global memory 10..30 times in a row (with those probes answered "no" the launch was 12 us shorter at 1 M spheres).  So
-        // a wave shares its lanes among its unnamed nodes -- 64, 32, 16 or 8 lanes per node -- and every step of the three searches
-        // (each looks for the end of a run of "yes": delta(i, i + dir * x) > threshold is monotone in x) asks that many places at
-        // once: the powers of two, then equal parts of what is left.  A fifth of the round trips, ~35 instructions per step for
-        // the whole wave, no barrier below the climb's.
-        // (Measured on the way: the searches compacted into the lanes of wave 0 behind two barriers: - 1 %; the same without
-        // barriers, after wave 0's own output: + 15 %; 7 places per step in every lane of wave 0: + 9 % -- 300 instructions per step.)
+        // A node the climb has named: everything is known, and its record goes out.  The others -- three in a hundred: their ranges
+        // cross the chunk's boundary -- leave their half box and their number for k_cross (the direction is in adj[]), and that is
+        // where this workgroup ends.  What those nodes still need is Karras' search, whose probes beyond a code window are dependent
+        // round trips to global memory (with those probes answered "no" the launch was 12 us shorter at 1 M spheres): up to round 7
+        // the waves that had such nodes searched here and held the workgroup's place on the CU meanwhile; the search needs
+        // nothing this workgroup computes and runs in a search workgroup of the same launch (SEARCH WAVE above).
+        // (Measured on the way, with the search in this workgroup: compacted into the lanes of wave 0 behind two barriers: - 1 %; the
+        // same without barriers, after wave 0's own output: + 15 %; 7 places per step in every lane of wave 0: + 9 %.)
         const bool inner = p < leaf_start;
         const bool named = inner && lds.oe[tid] != (unsigned char)tid;
         u32 skip, child_a;
@@ -814,73 +1058,6 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
             node_out((u32)tid, j, c0 + lds.split[tid], skip, child_a, false);
             record_out(p, j, skip, child_a, soa_get(lds.node, tid));
         } else if (inner) crossing_out(p, d_next > d_prev ? 1 : -1);
-        const u64 todo = __builtin_amdgcn_ballot_w64(inner && !named);
-        if (todo == 0) return;
-        const u32 cnt = (u32)__builtin_popcountll(todo);
-        const u32 lpn_log = cnt <= 1 ? 6u : cnt <= 2 ? 5u : cnt <= 4 ? 4u : 3u, lpn = 1u << lpn_log, groups = 64u >> lpn_log;
-        const u32 g = (u32)lane >> lpn_log, sub = (u32)lane & (lpn - 1u);
-        auto group_count = [&](bool yes) -> I {             // how many lanes of my group say yes
-            u64 m = __builtin_amdgcn_ballot_w64(yes) >> (g << lpn_log);
-            if (lpn < 64u) m &= (1ull << lpn) - 1ull;
-            return (I)__builtin_popcountll(m);
-        };
-        for (u32 base = 0; base < cnt; base += groups) {
-            const bool on = base + g < cnt;                  // my group has a node this round
-            u64 m = todo;
-            for (u32 b = 0; b < base + g && on; b++) m &= m - 1ull;
-            const u32 t = on ? (u32)w * COL_WAVE + (u32)__builtin_ctzll(m) : (u32)tid;
-            const u32 i = c0 + t, ci = codes.win[HALO + t];
-            const int dn = lds.adj[t + 1], dp = lds.adj[t];   // delta(i, i + 1), delta(i - 1, i)
-            const int dir = dn > dp ? 1 : -1, delta_min = min(dn, dp);
-            // is place x (0 = none) in the run?  one load per lane; LDS if every lane's place is in the window
-            auto yes_at = [&](I x, int thr) -> bool {
-                const I jk = (I)i + dir * x;
-                const bool inb = on && x > 0 && (u32)jk < n;
-                const u32 o = (u32)(jk - codes.w0);
-                const bool inwin = o < (u32)WIN;
-                u32 cj;
-                if (__builtin_amdgcn_ballot_w64(inb && !inwin) == 0) cj = codes.win[inwin ? o : 0u];
-                else cj = inb ? (inwin ? codes.win[o] : gcodes[jk]) : 0u;
-                const u32 d = min(ffbh_raw(ci ^ cj), 32u + ffbh_raw(i ^ (u32)jk));
-                return inb && (int)d > thr;
-            };
-            // the first power of two that is not in the range any more
-            I hi = 2;
-            {
-                bool more = on;
-                int e0 = 1;
-                while (__builtin_amdgcn_ballot_w64(more)) {
-                    const int e = e0 + (int)sub;
-                    const I x = (more && e < 31 && (1u << e) <= n) ? (I)(1u << e) : (I)0;
-                    const I yes = group_count(yes_at(x, delta_min));
-                    if (more) {
-                        hi = (I)(1u << (e0 + yes));
-                        more = yes == (I)lpn && e0 + (int)lpn < 31;
-                        e0 += (int)lpn;
-                    }
-                }
-            }
-            // the end of a run of yes between lo (in) and hi (out)
-            auto run_end = [&](I lo, I hi, int thr) -> I {
-                while (__builtin_amdgcn_ballot_w64(on && hi - lo > 1)) {
-                    const bool act = on && hi - lo > 1;
-                    const I step = (hi - lo + (I)lpn) / ((I)lpn + 1);
-                    const I x = lo + ((I)sub + 1) * step;
-                    const I yes = group_count(yes_at(act && x < hi ? x : (I)0, thr));
-                    if (act) { lo += yes * step; hi = min(hi, lo + step); }
-                }
-                return lo;
-            };
-            const I len = run_end(hi / 2, hi, delta_min);
-            const u32 j = (u32)((I)i + dir * len);
-            const int delta_node = delta(codes, i, ci, (I)j);
-            const I s = run_end((I)0, len, delta_node);
-            const u32 gamma = dir > 0 ? (u32)(i + s) : (u32)(i - s - 1);
-            if (on && sub == 0) {
-                node_out(t, j, gamma, skip, child_a, true);
-                links_store(bounds, (uint64_t)i, skip, child_a);
-            }
-        }
         return;
     }
     if (p >= leaf_start) return;                      // no barrier below this line
@@ -1188,7 +1365,8 @@ int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const 
     const u32 nchunks = L.count[0];
     bool ordered_by_chunk = false;       // the production k_chunk orders the traversal's packets itself; otherwise k_cross does
     if (n < (1u << 30) && !(g_dbg & DBG_WIDE)) {
-        const dim3 grid(nchunks + (walk_order ? 8u * COL_ORDER_SLICES : 0u) + (report_word ? 1u : 0u));
+        // [order_packets workgroups][chunk and search workgroups: PLACES][report workgroup]
+        const dim3 grid((walk_order ? 8u * COL_ORDER_SLICES : 0u) + place_blocks(nchunks) + (report_word ? 1u : 0u));
         if (nodes)
             k_chunk<T, int32_t><<<grid, dim3(C), 0, s>>>(
                 codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, n_dev, walk_order, order_mode,
