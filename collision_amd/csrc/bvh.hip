@@ -1368,6 +1368,10 @@ int col_collide_plan_dev(void *stream, const void *coords, const void *radii, ui
         const bool msd = sort_plan == COL_SORT_MSD && padded <= COL_MSD_MAX_N;
         // MSD: no scan launch either -- the Morton kernel also adds its counts into group sums and the pass works out its own
         // offsets (radix.hip, k_scatter FUSED).  The group sums are cleared by the bounds kernel when it runs here, else by a memset.
+        // The 1024-pair tile class (round 9) has no global pass at all: the Morton kernel leaves every tile sorted by the bucket digit
+        // with a table of (start, count) words, and each bucket's workgroup gathers its pieces itself (radix.hip, k_bucket_sort GATHER).
+        const bool gather = msd && tile == 1024;
+        const uint32_t mtile = gather && padded >= COL_GATHER_BIG_FROM ? 4096u : tile;      // the Morton kernel's tile (col_common.h)
         const uint32_t nsums = msd ? (uint32_t)(col_radix_msd_fused_bytes() / sizeof(uint32_t)) : 0u;
         if (msd && col_ceil_div(padded, tile) > (uint64_t)COL_MSD_GROUP * COL_MSD_GROUPS) return COL_EINVAL;    // (more tiles than group sums: no tile class does that)
         if (!partials) {
@@ -1376,9 +1380,10 @@ int col_collide_plan_dev(void *stream, const void *coords, const void *radii, ui
         } else if (msd)
             COL_HIP(hipMemsetAsync(msd_fused, 0, nsums * sizeof(uint32_t), s));
         if ((rc = col_morton_tile(stream, coords, radii, partials, parts, n, padded, coord_bytes, codes0, ids0, packed,
-                                  counter, (uint32_t *)sort_scratch, tile, (uint32_t)col_ceil_div(padded, tile), msd ? 22 : 0,
-                                  publish, n_dev, msd ? msd_fused : nullptr))) return rc;
-        if (msd) rc = col_radix_sort_msd_fused(stream, codes0, codes1, ids0, ids1, padded, sort_scratch, oversize, n_dev, msd_fused);
+                                  counter, (uint32_t *)sort_scratch, mtile, (uint32_t)col_ceil_div(padded, mtile), msd ? 22 : 0,
+                                  publish, n_dev, msd ? msd_fused : nullptr, gather ? 1 : 0))) return rc;
+        if (gather) rc = col_radix_sort_msd_gather(stream, codes0, codes1, ids0, ids1, n, padded, sort_scratch, oversize, n_dev, msd_fused, mtile);
+        else if (msd) rc = col_radix_sort_msd_fused(stream, codes0, codes1, ids0, ids1, padded, sort_scratch, oversize, n_dev, msd_fused);
         else rc = col_radix_sort_ex(stream, codes0, codes1, ids0, ids1, padded, 4, 4, sort_scratch, 0, 1);
         if (rc) return rc;
         // the LSD plan was taken where the MSD plan could apply: tell the caller how clustered the codes are (oversize[1])

@@ -61,7 +61,15 @@ extern "C" int col_minmax4_stage1_dev(void *stream, const void *rows, const uint
 extern "C" int col_morton_tile(void *stream, const void *coords, const void *radii, const void *partials, uint32_t parts,
                                uint32_t n, uint32_t padded, int coord_bytes, uint32_t *codes, uint32_t *ids, void *packed,
                                uint32_t *zero_word, uint32_t *hist0, uint32_t tile, uint32_t nblocks, int hist_shift,
-                               uint32_t *publish, const uint32_t *n_dev, uint32_t *gsum);
+                               uint32_t *publish, const uint32_t *n_dev, uint32_t *gsum,
+                               int sorted);     // sorted (1024- or 4096-code tiles, with gsum only): the tile leaves SORTED by the digit, see morton.hip
+// ... and the MSD finish that gathers its buckets from those sorted tiles (radix.hip, k_bucket_sort GATHER): no global pass
+extern "C" int col_radix_sort_msd_gather(void *stream, const uint32_t *tile_keys, uint32_t *keys_out, const uint32_t *tile_vals,
+                                         uint32_t *vals_out, uint32_t n_bound, uint64_t padded, void *scratch, uint32_t *oversize,
+                                         const uint32_t *n_dev, const uint32_t *gsum, uint32_t tile);
+// the tile of that plan: 4096 codes from COL_GATHER_BIG_FROM codes on (pieces of ~16 pairs instead of ~4: a 128-byte line of a
+// sorted tile then serves two or three buckets instead of eight), 1024 below, where 4096-code tiles would leave CUs idle
+#define COL_GATHER_BIG_FROM (768u << 10)
 #define COL_MSD_GROUP 32u       /* tiles per group sum of the fused MSD pass (radix.hip: MSD_GROUP) */
 #define COL_MSD_GROUPS 32u      /* group sums per digit: the fused pass takes at most COL_MSD_GROUP * COL_MSD_GROUPS tiles */
 extern "C" int col_minmax4_stage1_zero(void *stream, const void *rows, uint64_t n, int coord_bytes, void *partials, uint32_t *parts,
@@ -128,6 +136,34 @@ __device__ __forceinline__ u32 count_of(u32 n, const u32 *__restrict__ n_dev) { 
 // number of set bits of `mask` strictly below this lane
 __device__ __forceinline__ u32 mbcnt(u64 mask) {
     return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
+}
+
+// lanes of this wave whose 8-bit digit equals mine ("match-any").  For every bit the ballot of
+// that bit is XORed with my own bit replicated over the word: the result marks the lanes that
+// DIFFER from me in that bit; the eight results are ORed (v_or3) and complemented.  12 VALU per
+// 32-lane half instead of 16 for the and-chain formulation.
+__device__ __forceinline__ u64 match8(u32 d) {
+    // Three batches (masks, ballots, folds) instead of bit by bit: a v_cmp result needs two wait states
+    // before a VALU instruction may read it as an SGPR operand, and seven other compares hide them.
+    u32 m[8];
+    u64 bal[8];
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        m[b] = (u32)__builtin_amdgcn_sbfe(d, b, 1);                         // my bit, replicated
+        // (opaque to the optimiser: it otherwise derives the comparison from d again -- shift + sign test --
+        // instead of comparing the mask it already has: 5 instead of 4 VALU per bit)
+        asm("" : "+v"(m[b]));
+    }
+#pragma unroll
+    for (int b = 0; b < 8; b++) bal[b] = __builtin_amdgcn_ballot_w64(m[b] != 0);
+    u32 dlo = 0, dhi = 0;
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        // acc | (ballot ^ mine) in one v_bitop3 per half (truth table 0xF6 for (acc, ballot, mine))
+        dlo = __builtin_amdgcn_bitop3_b32(dlo, (u32)bal[b], m[b], 0xF6);
+        dhi = __builtin_amdgcn_bitop3_b32(dhi, (u32)(bal[b] >> 32), m[b], 0xF6);
+    }
+    return ~(((u64)dhi << 32) | dlo);
 }
 
 // inclusive wave scan (add) via shuffles; wave = 64 lanes

@@ -54,33 +54,7 @@ template <> struct Val<32> { typedef V32 T; };
 
 template <typename K> __device__ __forceinline__ u32 digit_of(K key, int shift) { return (u32)(key >> shift) & (RDIG - 1); }
 
-// lanes of this wave whose 8-bit digit equals mine ("match-any").  For every bit the ballot of
-// that bit is XORed with my own bit replicated over the word: the result marks the lanes that
-// DIFFER from me in that bit; the eight results are ORed (v_or3) and complemented.  12 VALU per
-// 32-lane half instead of 16 for the and-chain formulation.
-__device__ __forceinline__ u64 match8(u32 d) {
-    // Three batches (masks, ballots, folds) instead of bit by bit: a v_cmp result needs two wait states
-    // before a VALU instruction may read it as an SGPR operand, and seven other compares hide them.
-    u32 m[8];
-    u64 bal[8];
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        m[b] = (u32)__builtin_amdgcn_sbfe(d, b, 1);                         // my bit, replicated
-        // (opaque to the optimiser: it otherwise derives the comparison from d again -- shift + sign test --
-        // instead of comparing the mask it already has: 5 instead of 4 VALU per bit)
-        asm("" : "+v"(m[b]));
-    }
-#pragma unroll
-    for (int b = 0; b < 8; b++) bal[b] = __builtin_amdgcn_ballot_w64(m[b] != 0);
-    u32 dlo = 0, dhi = 0;
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        // acc | (ballot ^ mine) in one v_bitop3 per half (truth table 0xF6 for (acc, ballot, mine))
-        dlo = __builtin_amdgcn_bitop3_b32(dlo, (u32)bal[b], m[b], 0xF6);
-        dhi = __builtin_amdgcn_bitop3_b32(dhi, (u32)(bal[b] >> 32), m[b], 0xF6);
-    }
-    return ~(((u64)dhi << 32) | dlo);
-}
+// (match8, the "match-any" of a wave's 8-bit digits: col_common.h -- morton.hip ranks with it too)
 
 // ---- histogram: blocks handle `g` consecutive tiles and write g-entry rows per digit ----
 // Round 4.  The first version counted with LDS atomics on a plain 256-bin array: 64 lanes with ~57 distinct random digits
@@ -587,33 +561,159 @@ __device__ __forceinline__ void bucket_rank(BucketLds<BS_IT> &lds, const u32 (&k
     __syncthreads();
 }
 
-template <int BS_IT>
+// GATHER (round 9, the MSD plan below 1 Mi codes inside col_collide: col_radix_sort_msd_gather): there is NO global pass in front.
+// k_a / v_a hold the tiles of col_morton_tile(sorted) -- every tile (ga.tile = 1024 or 4096 codes) sorted by the bucket digit --
+// and `offsets` its table, offsets[t * 256 + d] = (start of digit d inside tile t) << 16 | count (real codes only),
+// nblocks = tiles <= BS_NT.  A tile belongs to 2^glog consecutive lanes (as many as the tile count leaves each tile of the
+// workgroup's 1024 threads, at most 16).
+// Workgroup d, first round trip: a tile's lanes load its word; the workgroup adds up the group sums of the digits below d
+// (the bucket's start) while one block scan over the counts places every tile's piece in the bucket and yields S.
+// Second round trip, the gather into LDS: a tile's lanes fetch its piece as aligned 16-byte vectors, lane `sub` the vectors
+// sub, sub + 2^glog, ... (GATHER_CHUNKS per lane and array, every load issued before the first use): they cover a piece of up
+// to gather_piece(glog) pairs at any 4-byte alignment -- 13 with one lane per tile.  Longer pieces (a clustered digit, an input
+// already in Morton order: up to a whole tile) are listed in LDS and copied by a wave each, lanes striding over the piece.
+// Then the three LDS passes as ever.
+// Pads (rows from the real count on) are in nobody's count: every workgroup writes its 256th of them by formula, whether the
+// count is on the device or not.  An oversize bucket is gathered into ga.x_keys / x_vals[start ...] (the sort scratch's
+// ping-pong copy, which nothing else uses under this plan; other workgroups still READ k_a / v_a) and takes the global
+// passes between there and k_b / v_b: x -> b -> x -> b.
+constexpr u32 GATHER_CHUNKS = 4, GATHER_GLOG_MAX = 4;
+__host__ __device__ constexpr u32 gather_piece(u32 glog) { return ((4u * GATHER_CHUNKS) << glog) - 3u; }
+struct GatherOff {};
+struct GatherOn { const u32 *gsum; u32 n_bound; u32 tile; u32 glog; u32 *x_keys, *x_vals; };
+template <bool GATHER> struct GatherArg { typedef GatherOff T; };
+template <> struct GatherArg<true> { typedef GatherOn T; };
+template <bool GATHER> __device__ __forceinline__ u32 *oversize_area(u32 *a, const typename GatherArg<GATHER>::T &ga, bool keys) {
+    if constexpr (GATHER) return keys ? ga.x_keys : ga.x_vals; else return a;
+}
+
+template <int BS_IT, bool GATHER = false>
 __global__ __launch_bounds__(BS_NT) void k_bucket_sort(u32 *__restrict__ k_a, u32 *__restrict__ v_a, u32 *__restrict__ k_b,
                                                         u32 *__restrict__ v_b, u32 n, const u32 *__restrict__ offsets,
-                                                        u32 nblocks, u32 *oversize, const u32 *__restrict__ n_real_dev) {
+                                                        u32 nblocks, u32 *oversize, const u32 *__restrict__ n_real_dev,
+                                                        typename GatherArg<GATHER>::T ga = {}) {
     constexpr u32 BS_CAP = BS_NT * BS_IT;
     constexpr int BS_ROW = COL_WAVE * BS_IT;       // positions per wave
     __shared__ BucketLds<BS_IT> lds;
     const u32 tid = threadIdx.x, lane = tid & (COL_WAVE - 1);
     const u32 w = (u32)__builtin_amdgcn_readfirstlane((int)(tid / COL_WAVE));
-    const u32 d = blockIdx.x;
-    const u32 start = offsets[(uint64_t)d * nblocks], end = d + 1 < RDIG ? offsets[(uint64_t)(d + 1) * nblocks] : n;
-    // DEVICE-SIDE COUNT (col_common.h): of the n pairs only the first *n_real_dev are real codes, the rest are pads
-    // (0xFFFFFFFF) -- possibly far more than a bucket holds when n is a capacity.  They sit at the END of bucket 255 in the order
-    // of their ids (the global pass is stable and they came last), i.e. sorted position j >= n_real holds the pad with id j:
-    // bucket 255 sorts its real codes only, and every workgroup writes its 256th of the pads (one workgroup copying 3 * 10^5
-    // of them through cost the one-rank step 0.14 ms).
-    u32 pads = 0;
-    if (n_real_dev) {
-        const u32 n_real = min(n, *n_real_dev), all = n - n_real, per = (all + RDIG - 1) / RDIG;
-        for (u32 i = threadIdx.x; i < per; i += BS_NT) {
-            const u32 j = n_real + d * per + i;
-            if (j < n) { k_b[j] = 0xFFFFFFFFu; v_b[j] = j; }
+    // GATHER: workgroups are dealt round-robin over the 8 XCDs, each with its own L2, and a 128-byte line of a sorted tile (32
+    // pairs) or of the table (32 digits) serves neighbouring buckets: every XCD takes 32 CONSECUTIVE buckets, so that a line
+    // is fetched into one L2 or two instead of all eight
+    const u32 d = GATHER ? (blockIdx.x & 7u) * (RDIG / 8) + (blockIdx.x >> 3) : blockIdx.x;
+    u32 start, S;
+    if constexpr (GATHER) {
+        static_assert(BS_NT >= MSD_GROUP * MSD_GROUPS && BS_NT == 4 * RDIG, "one thread per tile; four threads per digit column of the group sums");
+        u32 *const l_src = &lds.cnt[0][0], *const l_pos = l_src + BS_NT, *const l_cnt = l_src + 2 * BS_NT;   // the list of long pieces
+        u32 *const l_n = &lds.base[BS_NW];                                                                // ... and its length
+        // ---- first round trip: the table word of my tile, the group sums below this bucket ----
+        const u32 glog = ga.glog, sub = tid & ((1u << glog) - 1u), my_tile = tid >> glog;     // (nblocks << glog <= BS_NT)
+        const u32 word = my_tile < nblocks ? offsets[(uint64_t)my_tile * RDIG + d] : 0u;
+        const u32 ngroups = (nblocks + MSD_GROUP - 1) / MSD_GROUP;
+        u32 below = 0;
+        {
+            const u32 j = tid & (RDIG - 1), g0 = tid / RDIG;
+#pragma unroll
+            for (int m = 0; m < MSD_GROUPS / 4; m++) {
+                const u32 g = g0 + 4u * m;
+                if (j < d && g < ngroups) below += ga.gsum[g * RDIG + j];
+            }
         }
-        if (d == RDIG - 1) pads = min(end - start, all);
+        const u32 n_real = count_of(min(ga.n_bound, n), n_real_dev);
+        if (tid == 0) *l_n = 0;
+        // every workgroup writes its 256th of the pads: sorted position j >= n_real holds the pad with id j
+        {
+            const u32 all = n - n_real, per = (all + RDIG - 1) / RDIG;
+            for (u32 i = tid; i < per; i += BS_NT) {
+                const u32 j = n_real + d * per + i;
+                if (j < n) { k_b[j] = 0xFFFFFFFFu; v_b[j] = j; }
+            }
+        }
+        const u32 g_cnt = word & 0xFFFFu, g_src = my_tile * ga.tile + (word >> 16);
+        u32 g_pos;
+        {   // one scan (the pieces' places) and one sum (the bucket's start) behind the same barrier
+            const u32 one = sub == 0 ? g_cnt : 0u;        // (a tile's first lane counts for it)
+            const u32 incl = wave_incl_scan(one), bs = wave_sum(below);
+            if (lane == COL_WAVE - 1) lds.ws[w] = incl;
+            if (lane == 0) lds.base[w] = bs;
+            __syncthreads();
+            u32 pre = 0, tot = 0, st = 0;
+#pragma unroll
+            for (int i = 0; i < BS_NW; i++) {
+                const u32 s = lds.ws[i];
+                if ((u32)i < w) pre += s;
+                tot += s;
+                st += lds.base[i];
+            }
+            g_pos = (u32)__shfl((int)(pre + incl - one), (int)(lane & ~((1u << glog) - 1u)), COL_WAVE);     // ... and tells the others
+            S = tot;
+            start = st;
+        }
+        if (S == 0) return;
+        if (start + S > n_real) return;      // (never, with the table and the sums of one Morton launch: nothing is written out of bounds)
+        const bool fits = S <= BS_CAP;
+        u32 *const xk = ga.x_keys + start, *const xv = ga.x_vals + start;
+        // ---- second round trip: the gather ----
+        typedef u32 v4u __attribute__((ext_vector_type(4)));
+        const u32 a0 = g_src & ~3u, sh = g_src & 3u;        // the aligned vectors from a0 on; the piece is their words [sh, sh + g_cnt)
+        // (no vector may reach past the end of the arrays -- the last tile's piece can end in the last, partial vector -- or be misaligned)
+        const bool mine = g_cnt <= gather_piece(glog) && a0 + ((sh + g_cnt + 3u) & ~3u) <= n && (((uintptr_t)k_a | (uintptr_t)v_a) & 15u) == 0;
+        if (!mine && sub == 0 && g_cnt) {
+            const u32 e = atomicAdd(l_n, 1u);
+            l_src[e] = g_src; l_pos[e] = g_pos; l_cnt[e] = g_cnt;
+        }
+        v4u pk[GATHER_CHUNKS], pv[GATHER_CHUNKS];
+#pragma unroll
+        for (u32 c = 0; c < GATHER_CHUNKS; c++) {      // (unconditional loads, all in flight together: an unused vector reads words 0..3)
+            const u32 ci = (c << glog) + sub;
+            const u32 a = mine && 4u * ci < sh + g_cnt ? a0 + 4u * ci : 0u;
+            pk[c] = *reinterpret_cast<const v4u *>(k_a + a);
+            pv[c] = *reinterpret_cast<const v4u *>(v_a + a);
+        }
+#pragma unroll
+        for (u32 c = 0; c < GATHER_CHUNKS; c++) {
+#pragma unroll
+            for (u32 i = 0; i < 4; i++) {
+                const u32 j = 4u * ((c << glog) + sub) + i - sh;         // this word's place in the piece (wraps below the piece)
+                if (mine && j < g_cnt) {
+                    if (fits) { lds.keys[g_pos + j] = pk[c][i]; lds.vals[g_pos + j] = pv[c][i]; }
+                    else { xk[g_pos + j] = pk[c][i]; xv[g_pos + j] = pv[c][i]; }
+                }
+            }
+        }
+        __syncthreads();
+        const u32 nl = *l_n;
+        for (u32 e = w; e < nl; e += BS_NW) {
+            const u32 src = l_src[e], q = l_pos[e], c = l_cnt[e];
+            for (u32 j = lane; j < c; j += COL_WAVE) {
+                const u32 kk = k_a[src + j], vv = v_a[src + j];
+                if (fits) { lds.keys[q + j] = kk; lds.vals[q + j] = vv; }
+                else { xk[q + j] = kk; xv[q + j] = vv; }
+            }
+        }
+        if (!fits) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // the global passes below read what other threads gathered
+        __syncthreads();
+        if (!fits) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    } else {
+        start = offsets[(uint64_t)d * nblocks];
+        const u32 end = d + 1 < RDIG ? offsets[(uint64_t)(d + 1) * nblocks] : n;
+        // DEVICE-SIDE COUNT (col_common.h): of the n pairs only the first *n_real_dev are real codes, the rest are pads
+        // (0xFFFFFFFF) -- possibly far more than a bucket holds when n is a capacity.  They sit at the END of bucket 255 in the order
+        // of their ids (the global pass is stable and they came last), i.e. sorted position j >= n_real holds the pad with id j:
+        // bucket 255 sorts its real codes only, and every workgroup writes its 256th of the pads (one workgroup copying 3 * 10^5
+        // of them through cost the one-rank step 0.14 ms).
+        u32 pads = 0;
+        if (n_real_dev) {
+            const u32 n_real = min(n, *n_real_dev), all = n - n_real, per = (all + RDIG - 1) / RDIG;
+            for (u32 i = threadIdx.x; i < per; i += BS_NT) {
+                const u32 j = n_real + d * per + i;
+                if (j < n) { k_b[j] = 0xFFFFFFFFu; v_b[j] = j; }
+            }
+            if (d == RDIG - 1) pads = min(end - start, all);
+        }
+        S = end - start - pads;
+        if (S == 0) return;
     }
-    const u32 S = end - start - pads;
-    if (S == 0) return;
     u32 key[BS_IT], val[BS_IT], pos[BS_IT];
 
     if (S <= BS_CAP) {
@@ -623,8 +723,13 @@ __global__ __launch_bounds__(BS_NT) void k_bucket_sort(u32 *__restrict__ k_a, u3
         for (int k = 0; k < BS_IT; k++) {
             const u32 p = w * L + k * COL_WAVE + lane;
             const bool ok = (u32)k * COL_WAVE < L && p < S;
-            key[k] = ok ? k_a[start + p] : 0xFFFFFFFFu;
-            val[k] = ok ? v_a[start + p] : 0u;
+            if constexpr (GATHER) {        // (the bucket stands in LDS already)
+                key[k] = ok ? lds.keys[p] : 0xFFFFFFFFu;
+                val[k] = ok ? lds.vals[p] : 0u;
+            } else {
+                key[k] = ok ? k_a[start + p] : 0xFFFFFFFFu;
+                val[k] = ok ? v_a[start + p] : 0u;
+            }
         }
         for (int shift = 0; shift < BS_SHIFT; shift += 8) {
             bucket_rank<BS_IT>(lds, key, pos, S, shift, w, tid, L);
@@ -667,12 +772,13 @@ __global__ __launch_bounds__(BS_NT) void k_bucket_sort(u32 *__restrict__ k_a, u3
         return;
     }
 
-    // oversize bucket: the same three passes through global memory, a -> b -> a -> b
+    // oversize bucket: the same three passes through global memory, a -> b -> a -> b (GATHER: a = the area it was gathered into)
     if (tid == 0 && oversize) *oversize = S;
+    u32 *const o_k = oversize_area<GATHER>(k_a, ga, true), *const o_v = oversize_area<GATHER>(v_a, ga, false);
     int pass = 0;
     for (int shift = 0; shift < BS_SHIFT; shift += 8, pass++) {
-        const u32 *sk = ((pass & 1) ? k_b : k_a) + start, *sv = ((pass & 1) ? v_b : v_a) + start;
-        u32 *dk = ((pass & 1) ? k_a : k_b) + start, *dv = ((pass & 1) ? v_a : v_b) + start;
+        const u32 *sk = ((pass & 1) ? k_b : o_k) + start, *sv = ((pass & 1) ? v_b : o_v) + start;
+        u32 *dk = ((pass & 1) ? o_k : k_b) + start, *dv = ((pass & 1) ? o_v : v_b) + start;
         if (tid < RDIG) lds.base[tid] = 0;
         __syncthreads();
         for (u32 i = tid; i < S; i += BS_NT) atomicAdd(&lds.base[digit_of(sk[i], shift)], 1u);
@@ -1144,6 +1250,32 @@ int col_radix_sort_msd_fused(void *stream, const uint32_t *keys, uint32_t *keys_
         k_bucket_sort<8><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, starts, 1u, oversize, n_real_dev);
     else
         k_bucket_sort<16><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, starts, 1u, oversize, n_real_dev);
+    COL_LAUNCH_OK();
+    return COL_OK;
+}
+
+// The MSD plan of col_collide without ANY global pass, for the 1024-pair tile class (k_bucket_sort, GATHER): tile_keys / tile_vals
+// hold the tiles col_morton_tile(sorted) left sorted by the bucket digit, the start of `scratch` its table, `gsum` the group sums.
+// n_bound: the (bound of the) number of real codes, n_dev its device-side count or NULL; the rows from there to `padded` are pads.
+// The ping-pong copy of the sort scratch (unused otherwise under this plan) is where an oversize bucket is gathered.
+int col_radix_sort_msd_gather(void *stream, const uint32_t *tile_keys, uint32_t *keys_out, const uint32_t *tile_vals, uint32_t *vals_out,
+                              uint32_t n_bound, uint64_t padded, void *scratch, uint32_t *oversize, const uint32_t *n_dev,
+                              const uint32_t *gsum, uint32_t tile) {
+    if (padded == 0) return COL_OK;
+    if (!scratch || !tile_keys || !tile_vals || !keys_out || !vals_out || !gsum || n_bound > padded) return COL_EINVAL;
+    if ((tile != 1024 && tile != 4096) || tile < tile_auto(padded, 4, 4) || padded > COL_MSD_SMALL_N) return COL_EINVAL;     // (the table fits the scratch's histogram)
+    const size_t nb = col_ceil_div(padded, tile);
+    if (nb > (size_t)MSD_GROUP * MSD_GROUPS || nb > (size_t)BS_NT) return COL_EINVAL;
+    u32 glog = 0;
+    while (glog < GATHER_GLOG_MAX && (nb << (glog + 1)) <= (size_t)BS_NT) glog++;
+    char *p = (char *)scratch;
+    const u32 *table = (const u32 *)p; p += align256((size_t)RDIG * nb * sizeof(u32));
+    p += align256(col_scan_scratch_bytes((uint64_t)RDIG * nb));
+    u32 *x_keys = (u32 *)p;            p += align256((size_t)padded * 4);
+    u32 *x_vals = (u32 *)p;
+    const GatherOn ga{gsum, n_bound, tile, glog, x_keys, x_vals};
+    k_bucket_sort<8, true><<<dim3(RDIG), dim3(BS_NT), 0, col_stream(stream)>>>((u32 *)tile_keys, (u32 *)tile_vals, keys_out, vals_out, (u32)padded,
+                                                                                table, (u32)nb, oversize, n_dev, ga);
     COL_LAUNCH_OK();
     return COL_OK;
 }

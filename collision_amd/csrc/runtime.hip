@@ -47,7 +47,9 @@ const char *col_error_string(int code) {
     return "collision_hip: unknown error";
 }
 
-int col_version(void) { return 101; }     // 101: `nodes` may be NULL in col_lbvh and the col_collide family
+// 101: `nodes` may be NULL in col_lbvh and the col_collide family
+// 102: col_collide's intermediates codes0 / ids0 hold digit-sorted tiles on the MSD plan below 1 Mi codes (include/collision_hip.h)
+int col_version(void) { return 102; }
 
 int col_device_count(int *count) { COL_HIP(hipGetDeviceCount(count)); return COL_OK; }
 int col_set_device(int device) { COL_HIP(hipSetDevice(device)); return COL_OK; }

@@ -226,6 +226,11 @@ int col_lbvh(void *stream, const uint32_t *codes, const uint32_t *ids, const voi
  * enqueue DAG as one call.  codes/ids: two buffers of `padded` uint32 each
  * (sorted result in codes[1]/ids[1], as in the reference); nodes 2n-1
  * or NULL (see col_lbvh: nothing on this path reads them);
+ * codes[0]/ids[0] are intermediates.  They hold the codes and the id ramp in input order, EXCEPT on the
+ * COL_SORT_MSD plan with padded < 2^20 (col_version() >= 102): there every tile of 1024 consecutive rows
+ * (4096 from padded = 786 432 on) holds its (code, row index) pairs stably sorted by code bits 22..29, pads
+ * last -- the bucket finish gathers from these tiles, there is no global scatter pass.  ids[0] is then NOT
+ * range(padded);
  * bounds (2n-1)*8 scalars; flags 2n-1 uint32; scratch from
  * col_collide_scratch_bytes. */
 size_t col_collide_scratch_bytes(uint32_t n, uint32_t padded, int coord_bytes);
