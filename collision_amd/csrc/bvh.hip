@@ -47,29 +47,13 @@ template <typename T> __device__ __forceinline__ void link_store(T *bounds, uint
     reinterpret_cast<Bits *>(bounds)[row * 4 + 3] = (Bits)v;
 }
 
-// collision.cl:65-77 delta(i, j): common-prefix length of codes i and j, index bits as the
-// tie-break for equal codes, -1 outside [0, n).
-__device__ __forceinline__ int delta(const u32 *__restrict__ codes, u32 n, u32 i, u32 ci, int64_t j) {
-    if (j < 0 || j >= (int64_t)n) return -1;
-    const u32 cj = codes[j];
-    return ci != cj ? __clz((int)(ci ^ cj)) : 32 + __clz((int)(i ^ (u32)j));
-}
-
-// The right child whose range starts at leaf k (1 <= k <= n-1): internal node k if that
-// node's range runs forward from k, otherwise the single leaf k.
-__device__ __forceinline__ u32 right_child_at(const u32 *__restrict__ codes, u32 n, u32 k) {
-    if (k + 1 >= n) return (n - 1) + k;
-    const u32 ck = codes[k];
-    const bool fwd = delta(codes, n, k, ck, (int64_t)k + 1) > delta(codes, n, k, ck, (int64_t)k - 1);
-    return fwd ? k : (n - 1) + k;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void k_build(const u32 *__restrict__ codes, const u32 *__restrict__ ids,
                                                 col_node *__restrict__ nodes, T *__restrict__ bounds, u32 n) {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const u32 leaf_start = n - 1;
+    const auto code = [codes](int64_t k) { return codes[k]; };       // every probe reads global memory
 
     // collision.cl:55-63 (fillInternal fills the leaves)
     const u32 id = ids[i];
@@ -77,28 +61,14 @@ __global__ __launch_bounds__(256) void k_build(const u32 *__restrict__ codes, co
     nodes[leaf_start + i].data[0] = id;
     if (bounds) {
         const uint64_t row = 2ull * (leaf_start + i);
-        link_store(bounds, row, i + 1 < n ? right_child_at(codes, n, i + 1) : END);
+        link_store(bounds, row, i + 1 < n ? right_child_at(code, n, i + 1) : END);
         link_store(bounds, row + 1, id);
     }
     if (i >= leaf_start) return;
 
     // collision.cl:81-121 (Karras 2012)
-    const u32 ci = codes[i];
-    const int dir = delta(codes, n, i, ci, (int64_t)i + 1) > delta(codes, n, i, ci, (int64_t)i - 1) ? 1 : -1;
-    const int delta_min = delta(codes, n, i, ci, (int64_t)i - dir);
-    int64_t len_max = 2;
-    while (delta(codes, n, i, ci, (int64_t)i + dir * len_max) > delta_min) len_max *= 2;
-    int64_t len = 0;
-    for (int64_t t = len_max / 2; t > 0; t /= 2)
-        if (delta(codes, n, i, ci, (int64_t)i + dir * (len + t)) > delta_min) len += t;
-    const u32 j = (u32)((int64_t)i + dir * len);
-    const int delta_node = delta(codes, n, i, ci, (int64_t)j);
-    int64_t s = 0, t = len;
-    do {
-        t = (t + 1) / 2;
-        if (delta(codes, n, i, ci, (int64_t)i + dir * (s + t)) > delta_node) s += t;
-    } while (t > 1);
-    const u32 gamma = dir > 0 ? (u32)(i + s) : (u32)(i - s - 1);
+    u32 j, gamma;
+    karras_search(code, n, i, codes[i], j, gamma);
     const u32 lo = min(i, j), hi = max(i, j);
     const u32 child_a = (lo == gamma) ? leaf_start + gamma : gamma;
     const u32 child_b = (hi == gamma + 1) ? leaf_start + gamma + 1 : gamma + 1;
@@ -109,7 +79,7 @@ __global__ __launch_bounds__(256) void k_build(const u32 *__restrict__ codes, co
     nodes[child_a].parent = i;
     nodes[child_b].parent = i;
     if (bounds) {
-        link_store(bounds, 2ull * i, hi + 1 < n ? right_child_at(codes, n, hi + 1) : END);
+        link_store(bounds, 2ull * i, hi + 1 < n ? right_child_at(code, n, hi + 1) : END);
         link_store(bounds, 2ull * i + 1, child_a);      // (no leaf-block marks here: they need the boxes, see lbvh.hip)
     }
 }

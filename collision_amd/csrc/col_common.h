@@ -237,6 +237,40 @@ __device__ __forceinline__ void xcd_packet_range(u32 npackets, u32 x, u32 &p_lo,
     p_lo = (u32)(((u64)ng * x) >> 3) * COL_TRAV_WAVES;
     p_end = min((u32)(((u64)ng * (x + 1)) >> 3) * COL_TRAV_WAVES, npackets);
 }
+// ---- Karras' sequential search (collision.cl:65-121), one node per thread; shared by bvh.hip (k_build) and lbvh.hip
+// (k_chunk_wide).  `code(j)` fetches sorted code j, 0 <= j < n: how -- global memory, an LDS window -- is the caller's.
+// delta(i, j): common-prefix length of codes i and j (ci = code(i)), index bits as the tie-break for equal codes, -1 outside [0, n)
+template <typename Code> __device__ __forceinline__ int karras_delta(Code code, u32 n, u32 i, u32 ci, int64_t j) {
+    if (j < 0 || j >= (int64_t)n) return -1;
+    const u32 cj = code(j);
+    return ci != cj ? __clz((int)(ci ^ cj)) : 32 + __clz((int)(i ^ (u32)j));
+}
+// The right child whose range starts at leaf k (1 <= k <= n-1): internal node k if that node's range runs forward from k,
+// otherwise the single leaf k.
+template <typename Code> __device__ __forceinline__ u32 right_child_at(Code code, u32 n, u32 k) {
+    if (k + 1 >= n) return (n - 1) + k;
+    const u32 ck = code((int64_t)k);
+    const bool fwd = karras_delta(code, n, k, ck, (int64_t)k + 1) > karras_delta(code, n, k, ck, (int64_t)k - 1);
+    return fwd ? k : (n - 1) + k;
+}
+// internal node i (i + 1 < n, ci = code(i)): its other end j and its split gamma (the last leaf of its left child)
+template <typename Code> __device__ __forceinline__ void karras_search(Code code, u32 n, u32 i, u32 ci, u32 &j, u32 &gamma) {
+    const int dir = karras_delta(code, n, i, ci, (int64_t)i + 1) > karras_delta(code, n, i, ci, (int64_t)i - 1) ? 1 : -1;
+    const int delta_min = karras_delta(code, n, i, ci, (int64_t)i - dir);
+    int64_t len_max = 2;
+    while (karras_delta(code, n, i, ci, (int64_t)i + dir * len_max) > delta_min) len_max *= 2;
+    int64_t len = 0;
+    for (int64_t t = len_max / 2; t > 0; t /= 2)
+        if (karras_delta(code, n, i, ci, (int64_t)i + dir * (len + t)) > delta_min) len += t;
+    j = (u32)((int64_t)i + dir * len);
+    const int delta_node = karras_delta(code, n, i, ci, (int64_t)j);
+    int64_t s = 0, t = len;
+    do {
+        t = (t + 1) / 2;
+        if (karras_delta(code, n, i, ci, (int64_t)i + dir * (s + t)) > delta_node) s += t;
+    } while (t > 1);
+    gamma = dir > 0 ? (u32)(i + s) : (u32)(i - s - 1);
+}
 // ---- 30-bit Morton codes (collision.cl:14-31); shared by morton.hip and multi.hip ----
 __device__ __forceinline__ u32 expand_bits(u32 v) {   // collision.cl:14-20
     v = (v * 0x00010001u) & 0xFF0000FFu;

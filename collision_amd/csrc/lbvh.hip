@@ -19,8 +19,8 @@
 //             lies in this chunk (`partial`: the prefix / suffix unions of the chunk's leaf boxes);
 //             Karras' search for its other end, split and links runs in a search workgroup of the
 //             same launch (a wave per chunk, sorted codes staged in an LDS window chunk +- 256 for
-//             the dependent probes).  (The wide-index instance, n >= 2^30, searches for every node
-//             in the chunk's own workgroup and waits in LDS for the children.)
+//             the dependent probes).  (From 2^30 leaves on k_chunk_wide takes its place: 64-bit positions, Karras'
+//             search for every node in the chunk's own workgroup, which waits in LDS for the children.)
 //   k_group   (above COL_MSD_MAX_N / 256 chunks only; 1-2 tiny launches) sparse tables over chunk totals,
 //             256 chunks per group, then over group totals, ...
 //   k_cross   the ~1-2 % of nodes that cross chunks: partial[first] U partial[last] U the whole chunks in
@@ -37,7 +37,6 @@
 // internal node has that index) stores its prefix itself.
 #include "col_common.h"
 #include <math.h>
-#include <type_traits>
 
 namespace {
 
@@ -74,6 +73,13 @@ template <typename T> __device__ __forceinline__ void box_merge(Box<T> &a, const
         a.lo[k] = hw_min(a.lo[k], o.lo[k]);
         a.hi[k] = hw_max(a.hi[k], o.hi[k]);
     }
+}
+// (component by component: a reference to one of two boxes would keep both in memory)
+template <typename T> __device__ __forceinline__ Box<T> box_select(bool c, const Box<T> &a, const Box<T> &b) {
+    Box<T> r;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { r.lo[k] = c ? a.lo[k] : b.lo[k]; r.hi[k] = c ? a.hi[k] : b.hi[k]; }
+    return r;
 }
 
 // global table / partial entry: two vec4 rows (lo.xyz, -) (hi.xyz, -)
@@ -141,62 +147,30 @@ template <typename T> __device__ __forceinline__ Box<T> gtab_query(const T *tab,
 // search run at LDS latency; probes outside the window fall back to global memory.
 constexpr int HALO = 256;
 constexpr int WIN = C + 2 * HALO;
-// I: the type of a (possibly out-of-range) leaf position in the Karras search: int32_t below 2^30 leaves --
-// i +- 2 * range cannot overflow it, and 32-bit index arithmetic is half the vector instructions -- else int64_t
+// (an LDS pointer by type: as a generic pointer the two sides of a window-or-global read become ONE flat_load)
 typedef __attribute__((address_space(3))) const u32 LdsWord;
-// FAST (32-bit positions only): delta() without per-lane branches, see below.
-template <typename I, bool FAST = false> struct Codes {
-    const u32 *__restrict__ g;
-    LdsWord *win;              // (an LDS pointer by type: as a generic pointer the two sides of at() become ONE flat_load)
-    I w0;
-    u32 n;
-    __device__ __forceinline__ u32 at(I j) const {          // 0 <= j < n
-        if constexpr (FAST && sizeof(I) == 4) {
-            // one wave-uniform branch instead of a branch per lane (see delta() below)
-            const u32 o = (u32)(j - w0);
-            const bool inwin = o < (u32)WIN;
-            if (__builtin_amdgcn_ballot_w64(!inwin) == 0) return win[o];
-            return inwin ? win[o] : g[j];
-        } else {
-            const I o = j - w0;
-            return (o >= 0 && o < WIN) ? win[o] : g[j];
-        }
-    }
-};
 // v_ffbh_u32: leading zeros, 0xFFFFFFFF for 0
 __device__ __forceinline__ u32 ffbh_raw(u32 x) { u32 r; asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(x)); return r; }
-// collision.cl:65-77
-template <typename I, bool FAST> __device__ __forceinline__ int delta(const Codes<I, FAST> &c, u32 i, u32 ci, I j) {
-    if constexpr (FAST && sizeof(I) == 4) {
-        // The plain form below compiles to three nested per-lane branches (range check, window or global memory, equal
-        // codes): ~40 instructions per probe, a third of them scalar EXEC bookkeeping, and a wave makes ~28 probes.  Here:
-        // one wave-uniform branch (does ANY lane's probe leave the code window?  almost never), an unconditional LDS read, and
-        // the tie rule as an unsigned minimum -- clz(ci ^ cj) is 0xFFFFFFFF exactly when the codes are equal, and then
-        // 32 + clz(i ^ j) (j != i in every probe, so that is at most 63) is the smaller one.
-        const bool inb = (u32)j < c.n;                     // 0 <= j < n
-        const u32 o = (u32)(j - c.w0);
+// collision.cl:65-77 for two codes that are in range, the tie rule as an unsigned minimum -- clz(ci ^ cj) is 0xFFFFFFFF exactly
+// when the codes are equal, and then 32 + clz(i ^ j) (j != i in every probe, so that is at most 63) is the smaller one
+__device__ __forceinline__ u32 delta_of(u32 i, u32 ci, u32 j, u32 cj) { return min(ffbh_raw(ci ^ cj), 32u + ffbh_raw(i ^ j)); }
+// SEARCH WAVE's probes (32-bit positions: below 2^30 leaves i +- 2 * range cannot overflow them, and 32-bit index arithmetic
+// is half the vector instructions).  The plain form -- range check, window or global memory, equal codes -- compiles to three
+// nested per-lane branches: ~40 instructions per probe, a third of them scalar EXEC bookkeeping, and a wave makes ~28 probes.
+// Here: one wave-uniform branch (does ANY lane's probe leave the code window?  almost never) and an unconditional LDS read.
+struct CodeWindow {
+    const u32 *__restrict__ g;
+    LdsWord *win;
+    int32_t w0;
+    // code j; `inb`: this lane asks and 0 <= j < n (any other lane gets a word it must not use)
+    __device__ __forceinline__ u32 at(int32_t j, bool inb) const {
+        const u32 o = (u32)(j - w0);
         const bool inwin = o < (u32)WIN;
-#ifdef COL_EXP_NO_FAR      // timing experiment: no probe leaves the code window (wrong trees)
-        if (!inwin) return -1;
-#endif
-        u32 cj;
-        if (__builtin_amdgcn_ballot_w64(inb && !inwin) == 0) cj = c.win[inwin ? o : 0u];
-        else cj = inb ? (inwin ? c.win[o] : c.g[j]) : 0u;
-        const u32 d = min(ffbh_raw(ci ^ cj), 32u + ffbh_raw(i ^ (u32)j));
-        return inb ? (int)d : -1;
-    } else {
-        if (j < 0 || j >= (I)c.n) return -1;
-        const u32 cj = c.at(j);
-        return ci != cj ? __clz((int)(ci ^ cj)) : 32 + __clz((int)(i ^ (u32)j));
+        if (__builtin_amdgcn_ballot_w64(inb && !inwin) == 0) return win[inb ? o : 0u];
+        return inb ? (inwin ? win[o] : g[j]) : 0u;
     }
-}
-// the right child that starts at leaf k (see bvh.hip)
-template <typename I, bool FAST> __device__ __forceinline__ u32 right_child_at(const Codes<I, FAST> &c, u32 k) {
-    if (k + 1 >= c.n) return (c.n - 1) + k;
-    const u32 ck = c.at((I)k);
-    const bool fwd = delta(c, k, ck, (I)k + 1) > delta(c, k, ck, (I)k - 1);
-    return fwd ? k : (c.n - 1) + k;
-}
+    __device__ __forceinline__ u32 delta(u32 i, u32 ci, int32_t j, bool inb) const { return delta_of(i, ci, (u32)j, at(j, inb)); }
+};
 
 template <typename T>
 __device__ __forceinline__ void record_store(T *bounds, uint64_t node, const Box<T> &b, u32 skip, u32 down) {
@@ -218,27 +192,35 @@ template <typename T> __device__ __forceinline__ void links_store(T *bounds, uin
     p[7] = (Bits)down;
 }
 
-// LDS image of one chunk: the leaves, finished boxes of in-chunk internal nodes, ready flags / meeting places.
-// Round 4, second half: the image is PACKED so that more workgroups than the CU's 32 wave slots admit fit its LDS (f32: 14.9 KB
-// = 12 granules of 1280 B: ten workgroups; it was 19.7 KB: eight) -- the waves of a workgroup that have no crossing node leave
-// right after their stores while the others search, and the wave slots they free are only of use to a NEW workgroup if the
-// LDS has room for it; float64 (25.3 KB, was 31.4) gets six workgroups per CU instead of five.
+// LDS image of one chunk in k_chunk: the leaves, the finished boxes of the in-chunk internal nodes, the climb's tables.
+// The image is PACKED so that more workgroups than the CU's 32 wave slots admit fit its LDS (f32: 11.4 KB, under the 12 KB
+// of a search workgroup's windows; f64: 21.6 KB): a wave slot that a finished wave frees is only of use to a NEW
+// workgroup if the LDS has room for it.
 //   leaf[4][C]  the leaf's sphere (x, y, z, r), not its box: the box is c -+ r wherever it is read -- the same two IEEE
 //               operations on the same operands as in the leaf's own thread, so the same bits -- and a third less LDS
-//   flags       the wide-index instance's ready[C + 1] ([C] = 1 for ever: the 'flag' of a child that is a leaf); CLIMB: meet[],
-//               two 16-bit places per word (a value is a far end + 1 <= 256; the first arrival ORs it into a zero place and
+//   meet        two 16-bit places per word (a value is a far end + 1 <= 256; the first arrival ORs it into a zero place and
 //               sees zero, the second sees the first's value -- and spoils the place, which nobody reads again)
 //   adj         one signed byte per delta (-1 .. 63)
-//   oe, split   CLIMB: other end and split of node c0 + t as chunk-local positions in a byte each; oe[t] == t = not an
+//   oe, split   other end and split of node c0 + t as chunk-local positions in a byte each; oe[t] == t = not an
 //               in-chunk node (a node's range holds two leaves or more: its other end is never itself)
-template <typename T, bool CLIMB> struct ChunkLds {
+template <typename T> struct ChunkLds {
     T leaf[4][C];
     T node[6][C];
     T wave_tot[2][C / COL_WAVE][6];     // per-wave totals for the prefix / suffix scans
-    u32 flags[CLIMB ? C / 2 : C + 1];
+    u32 meet[C / 2];
     u32 ncross;                         // nodes of this chunk that cross its boundary, so far (see CROSS_CAP)
-    signed char adj[C + 4];             // adj[1 + t] = delta(p, p + 1) of the chunk's position t, adj[0] = delta(c0 - 1, c0) (FAST_DELTA: see k_chunk)
-    unsigned char oe[CLIMB ? C : 4], split[CLIMB ? C : 4];
+    signed char adj[C + 4];             // adj[1 + t] = delta(p, p + 1) of the chunk's position t, adj[0] = delta(c0 - 1, c0), adj[C + 1]: see k_chunk
+    unsigned char oe[C], split[C];
+};
+// ... and in k_chunk_wide: the same leaves, node boxes and wave totals; a ready flag per node (ready[C] = 1 for ever: the
+// 'flag' of a child that is a leaf); the sorted codes c0 - HALO .. c0 + C + HALO
+template <typename T> struct WideLds {
+    T leaf[4][C];
+    T node[6][C];
+    T wave_tot[2][C / COL_WAVE][6];
+    u32 ready[C + 1];
+    u32 ncross;
+    u32 win[WIN];
 };
 template <typename T> __device__ __forceinline__ Box<T> leaf_get(const T (&a)[4][C], int pos) {
     const T x = a[0][pos], y = a[1][pos], z = a[2][pos], r = a[3][pos];
@@ -383,7 +365,7 @@ struct __attribute__((packed, aligned(4))) LeafTail { u32 right_edge, id; };
 struct __attribute__((packed, aligned(4))) InnerTail { u32 right_edge, child_a, child_b; };
 
 // WALK ORDER (col_common.h), workgroup `ob` of the 8 x COL_ORDER_SLICES that order the packets of the traversal that follows: part of
-// k_chunk's launch (the first workgroups of its grid: done long before the launch is) or, with the wide-index instance of k_chunk, of
+// k_chunk's launch (the first workgroups of its grid: done long before the launch is) or, with k_chunk_wide, of
 // k_cross's (where they were first, and made that launch 11 us instead of 5 at 1 M spheres).  n: this call's number of leaves.
 constexpr u32 COL_ORDER_SLICES = 8;     // workgroups per XCD that order its packets
 constexpr u32 COL_DEAL_UPTO = COL_DEAL_MAX_N / 512;      // packets per XCD up to which a sparse scene's long walks are dealt
@@ -520,59 +502,137 @@ __device__ __forceinline__ void order_packets(u32 ob, u32 n, u32 n_bound, u32 *_
 // LDS of the production k_chunk: what a workgroup holds depends on its place in the grid -- a chunk's image, a code window for
 // each of the four chunks a search workgroup serves, or the bucket report's 257 words
 template <typename T> union ProdLds {
-    ChunkLds<T, true> chunk;
+    ChunkLds<T> chunk;
     u32 win[C / COL_WAVE][WIN];
     u32 report[C + 1];
 };
-template <typename T> __device__ __forceinline__ ChunkLds<T, true> &chunk_lds(ProdLds<T> &u) { return u.chunk; }
-template <typename T> __device__ __forceinline__ ChunkLds<T, false> &chunk_lds(ChunkLds<T, false> &c) { return c; }
-// PLACES.  The production k_chunk's grid behind its order_packets workgroups holds chunk workgroups and search workgroups (SEARCH
-// WAVE below: a wave per chunk, four chunks to a workgroup).  blockIdx % 8 is the XCD, each XCD builds one contiguous run of the
-// chunks, and a chunk's searcher runs on the chunk's XCD: it reads its code window from the same L2.  Four layouts were timed
-// (EXPERIMENTS R8; -DCOL_SEARCH_PLACE=k builds one of them at every size, for two builds alternating on one box):
-//   0  [all chunk workgroups][all search workgroups]   the searchers fill the drain of the last round: slower than no split
-//   1  [all search workgroups][all chunk workgroups]   the fastest step at 1 M spheres and on config 3; at 16 M the searchers are
-//                                                      7.6 rounds of resident waves before the first chunk starts: col_lbvh + 6.7 %
-//   2  groups of 40: [8 search workgroups, one per XCD][32 chunk workgroups] -- the searchers of the group's own 32 chunks
-//   3  groups of 40: [32 chunk workgroups][8 search workgroups]   the fastest from 2 M spheres up (2 and 3 are equal there)
-// Kept: 1 up to SEARCH_FIRST_MAX_CHUNKS chunks -- the searchers are then less than one round of the CUs' wave places --, 3 above.
-constexpr u32 SEARCH_FIRST_MAX_CHUNKS = 1500000 / C;           // between the measured sizes: 1 M (layout 1 wins) and 2 M (layout 3)
+// PLACES.  k_chunk's grid behind its order_packets workgroups holds chunk workgroups and search workgroups (SEARCH WAVE below: a
+// wave per chunk, four chunks to a workgroup).  blockIdx % 8 is the XCD, each XCD builds one contiguous run of the chunks, and a
+// chunk's searcher runs on the chunk's XCD: it reads its code window from the same L2.  Two layouts, chosen by the chunk count:
+//   searchers first  [all search workgroups][all chunk workgroups]   the fastest step at 1 M spheres and on config 3; at 16 M the
+//                    searchers are 7.6 rounds of resident waves before the first chunk starts: col_lbvh + 6.7 %
+//   groups of 40     [32 chunk workgroups][8 search workgroups, one per XCD: the searchers of the group's own 32 chunks]
+//                    the fastest from 2 M spheres up
+// Searchers first up to SEARCH_FIRST_MAX_CHUNKS chunks -- they are then less than one round of the CUs' wave places --, groups
+// above.  (Timed and dropped, EXPERIMENTS R8: all searchers LAST only fill the drain of the last round, slower than no split;
+// groups with their searchers in FRONT equal the groups kept.)
+constexpr u32 SEARCH_FIRST_MAX_CHUNKS = 1500000 / C;           // between the measured sizes: 1 M (searchers first wins) and 2 M (groups)
 constexpr u32 SEARCH_CHUNKS = C / COL_WAVE;                     // chunks per search workgroup
 constexpr u32 PLACE_CHUNKS = 8u * SEARCH_CHUNKS, PLACE_GROUP = PLACE_CHUNKS + 8u;      // 32 chunk workgroups and their 8 search workgroups
-__host__ __device__ __forceinline__ u32 place_layout(u32 chunks) {
-#ifdef COL_SEARCH_PLACE
-    return COL_SEARCH_PLACE;
-#else
-    return chunks <= SEARCH_FIRST_MAX_CHUNKS ? 1u : 3u;
-#endif
-}
 // number of chunk + search workgroups for `chunks` chunks (a bound, under a device-side count)
 __host__ __device__ __forceinline__ u32 place_blocks(u32 chunks) {
-    if (place_layout(chunks) >= 2u) return PLACE_GROUP * ((chunks + PLACE_CHUNKS - 1u) / PLACE_CHUNKS);
-    // (a multiple of 8 search workgroups, so that every XCD gets the same number wherever in the grid they start)
+    if (chunks > SEARCH_FIRST_MAX_CHUNKS) return PLACE_GROUP * ((chunks + PLACE_CHUNKS - 1u) / PLACE_CHUNKS);
+    // (a multiple of 8 search workgroups, so that every XCD gets the same number)
     return chunks + 8u * (((chunks + 7u) / 8u + SEARCH_CHUNKS - 1u) / SEARCH_CHUNKS);
 }
 // workgroup v of those: a chunk workgroup (its number `bid` among them; bid % 8 is its XCD) or search workgroup `m` of XCD `xcd`
 struct Place { bool searcher; u32 bid, xcd, m; };
 __device__ __forceinline__ Place place_of(u32 v, u32 chunks) {
-    const u32 layout = place_layout(chunks);
-    Place pl = {false, v, 0u, 0u};
-    if (layout >= 2u) {
+    Place pl;
+    if (chunks > SEARCH_FIRST_MAX_CHUNKS) {
         const u32 grp = v / PLACE_GROUP, within = v % PLACE_GROUP;
-        pl.searcher = layout == 2u ? within < 8u : within >= PLACE_CHUNKS;
-        pl.bid = grp * PLACE_CHUNKS + within - (layout == 2u ? 8u : 0u);
+        pl.searcher = within >= PLACE_CHUNKS;
+        pl.bid = grp * PLACE_CHUNKS + within;
         pl.xcd = within & 7u;
         pl.m = grp;
     } else {
-        const u32 nsearch = place_blocks(chunks) - chunks, sfirst = layout == 1u ? 0u : chunks;
-        pl.searcher = v - sfirst < nsearch;
-        pl.bid = layout == 1u ? v - nsearch : v;
-        // (sfirst need not be a multiple of 8: XCD x's first search workgroup is the first at or behind sfirst with v % 8 == x)
-        const u32 u = v - (sfirst & ~7u);
-        pl.xcd = u & 7u;
-        pl.m = (u >> 3) - (pl.xcd < (sfirst & 7u) ? 1u : 0u);
+        const u32 nsearch = place_blocks(chunks) - chunks;
+        pl.searcher = v < nsearch;
+        pl.bid = v - nsearch;
+        pl.xcd = v & 7u;
+        pl.m = v >> 3;
     }
     return pl;
+}
+// XCD-aware order: blockIdx % 8 is the XCD (each with its own L2).  Every XCD builds one contiguous run of the nb chunks -- the
+// same eighth of the sorted leaves whose packets it walks in k_traverse, and neighbouring chunks read overlapping codes: XCD x's
+// run has xcd_chunks(nb, x) chunks, xcd_chunk(nb, x, k) is its k-th.  Same bits; whole path, interleaved A/B of two builds on one
+// box: 1 M uniform 0.1706-0.1736 against 0.1744-0.1757 ms, 2 M 0.293-0.296 against 0.298-0.301, 16 M and config 3 unchanged; a
+// clustered scene at 2 M loses 2.5 % (the deep chunks of a cluster all go to one XCD; strips of 16 chunks going round the XCDs
+// avoid that and gain 0.4 % instead of 1.5 %: not taken).
+__device__ __forceinline__ u32 xcd_chunks(u32 nb, u32 x) { return nb / 8 + (x < nb % 8 ? 1u : 0u); }
+__device__ __forceinline__ u32 xcd_chunk(u32 nb, u32 x, u32 k) { const u32 q = nb / 8, r = nb % 8; return x * q + (x < r ? x : r) + k; }
+
+// ---- what k_chunk and k_chunk_wide share: a chunk workgroup's leaves and the words a finished node leaves behind ----
+// leaf tid of the chunk (sphere `id`; valid: it exists): its sphere into the LDS image, returns its box (empty if not valid).
+// collision.cl:128-141 (leafBounds)
+template <typename T>
+__device__ __forceinline__ Box<T> leaf_in(const T *__restrict__ coords, const T *__restrict__ radii, const T *__restrict__ packed,
+                                          bool valid, u32 id, int tid, T (&image)[4][C]) {
+    typedef typename BT<T>::V4 V4;
+    Box<T> leaf = box_empty<T>();
+    if (valid) {
+        V4 c;
+        T r;
+        if (packed) {                 // (x, y, z, r) rows written by col_morton_ex: one gather per leaf
+            c = reinterpret_cast<const V4 *>(packed)[id];
+            r = c.w;
+        } else {
+            c = reinterpret_cast<const V4 *>(coords)[id];
+            r = radii[id];
+        }
+        leaf.lo[0] = c.x - r; leaf.lo[1] = c.y - r; leaf.lo[2] = c.z - r;
+        leaf.hi[0] = c.x + r; leaf.hi[1] = c.y + r; leaf.hi[2] = c.z + r;
+        image[0][tid] = c.x; image[1][tid] = c.y; image[2][tid] = c.z; image[3][tid] = r;      // (a place beyond n is never read)
+    }
+    return leaf;
+}
+// The chunk-wide prefix / suffix unions from the waves' inclusive ones: every wave has left its totals, and behind a barrier
+// every thread folds in the totals of the waves before / behind its own.
+template <typename T>
+__device__ __forceinline__ void wave_totals_fold(const T (&wave_tot)[2][C / COL_WAVE][6], int w, Box<T> &pre, Box<T> &suf) {
+    for (int ww = 0; ww < C / COL_WAVE; ww++) {
+        Box<T> t;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { t.lo[k] = wave_tot[ww < w ? 0 : 1][ww][k]; t.hi[k] = wave_tot[ww < w ? 0 : 1][ww][3 + k]; }
+        if (ww < w) box_merge(pre, t);
+        if (ww > w) box_merge(suf, t);
+    }
+}
+// node i with its other end j and its split gamma: the node record's tail and the children's parent words (NODES); returns the
+// left child (collision.cl:104-120)
+template <bool NODES>
+__device__ __forceinline__ u32 node_children(col_node *__restrict__ nodes, u32 leaf_start, u32 i, u32 j, u32 gamma) {
+    const u32 lo = min(i, j), hi = max(i, j);
+    const bool a_leaf = lo == gamma, b_leaf = hi == gamma + 1;
+    const u32 child_a = a_leaf ? leaf_start + gamma : gamma;
+    const u32 child_b = b_leaf ? leaf_start + gamma + 1 : gamma + 1;
+    if constexpr (NODES) {
+        InnerTail tail = {hi, child_a, child_b};
+        *reinterpret_cast<InnerTail *>(&nodes[i].right_edge) = tail;
+        nodes[child_a].parent = i;
+        nodes[child_b].parent = i;
+    }
+    return child_a;
+}
+// a node whose range [i, j] lies in chunk c0 / C: its record with the box, marked as a leaf block if it is small and dense
+template <typename T>
+__device__ __forceinline__ void record_out(T *__restrict__ bounds, const T (&image)[4][C], u32 c0, u32 n, T block_k,
+                                           u32 i, u32 j, u32 skip, u32 child_a, const Box<T> &box) {
+    // leaf block (col_common.h): a small DENSE node -- on every axis at most block_k times as wide as its first
+    // leaf -- is marked for the packet walk.  Sparse scenes (BASELINE config 2: leaf boxes a fifth of the
+    // spacing) get no marks and walk as before; where spheres overlap in heaps (config 3) nearly every node
+    // of <= 16 leaves qualifies.
+    const u32 lo = min(i, j), hi = max(i, j);
+    u32 down = child_a;
+    if (hi - lo < COL_LEAF_BLOCK && n <= COL_LEAF_BLOCK_MAX_N && block_k > (T)0) {
+        const Box<T> first = leaf_get(image, (int)(lo - c0));
+        bool dense = true;
+#pragma unroll
+        for (int k = 0; k < 3; k++) dense = dense && (box.hi[k] - box.lo[k]) <= block_k * (first.hi[k] - first.lo[k]);
+        if (dense) down = block_link(lo, hi);
+    }
+    record_store(bounds, (uint64_t)i, box, skip, down);
+}
+// a node that crosses its chunk's boundary leaves this chunk's half of its range (`half`: the suffix from i if it runs forward,
+// the prefix up to i if backward) and its number for k_cross; returns its slot in the chunk's list (CROSS_CAP - 1 or more: no
+// slot, the chunk is dense)
+template <typename T>
+__device__ __forceinline__ u32 crossing_out(T *__restrict__ partial, u32 *__restrict__ cross, u32 *ncross, u32 chunk, u32 i, const Box<T> &half) {
+    box_store(partial, i, half);
+    const u32 slot = atomicAdd(ncross, 1u);
+    cross[(uint64_t)chunk * CROSS_CAP + (slot < CROSS_CAP - 1 ? slot : CROSS_CAP - 1)] = slot < CROSS_CAP - 1 ? i : CROSS_DENSE;
+    return slot;
 }
 
 // SEARCH WAVE (round 8).  Karras' search for the nodes of chunk c0 / C whose range crosses the chunk's boundary -- their other end,
@@ -591,7 +651,7 @@ __device__ __forceinline__ void search_wave(const u32 *__restrict__ gcodes, col_
                                             u32 *__restrict__ other_end, u32 n, u32 c0, u32 *win) {
     typedef int32_t I;
     const u32 lane = lane_id(), leaf_start = n - 1;
-    Codes<I, true> codes = {gcodes, (LdsWord *)win, (I)c0 - HALO, n};
+    const CodeWindow codes = {gcodes, (LdsWord *)win, (I)c0 - HALO};
     // the code window: every load first, one wait (see k_chunk)
     u32 wcode[WIN / COL_WAVE];
 #pragma unroll
@@ -610,7 +670,7 @@ __device__ __forceinline__ void search_wave(const u32 *__restrict__ gcodes, col_
     auto adj_at = [&](u32 u) -> int {                       // delta(c0 + u - 1, c0 + u), 0 <= u <= C + 1
         const u32 pos = c0 + u;
         if (pos < 1u || pos >= n) return -1;
-        return (int)min(ffbh_raw(codes.win[HALO + u - 1u] ^ codes.win[HALO + u]), 32u + ffbh_raw((pos - 1u) ^ pos));
+        return (int)delta_of(pos - 1u, codes.win[HALO + u - 1u], pos, codes.win[HALO + u]);
     };
     int a[5];                                               // adj[4 * lane + e]
 #pragma unroll
@@ -670,12 +730,7 @@ __device__ __forceinline__ void search_wave(const u32 *__restrict__ gcodes, col_
         auto yes_at = [&](I x, int thr) -> bool {
             const I jk = (I)i + dir * x;
             const bool inb = on && x > 0 && (u32)jk < n;
-            const u32 o = (u32)(jk - codes.w0);
-            const bool inwin = o < (u32)WIN;
-            u32 cj;
-            if (__builtin_amdgcn_ballot_w64(inb && !inwin) == 0) cj = codes.win[inwin ? o : 0u];
-            else cj = inb ? (inwin ? codes.win[o] : gcodes[jk]) : 0u;
-            const u32 d = min(ffbh_raw(ci ^ cj), 32u + ffbh_raw(i ^ (u32)jk));
+            const u32 d = codes.delta(i, ci, jk, inb);        // (every lane: a wave-uniform branch inside)
             return inb && (int)d > thr;
         };
         // the first power of two that is not in the range any more
@@ -707,21 +762,14 @@ __device__ __forceinline__ void search_wave(const u32 *__restrict__ gcodes, col_
         };
         const I len = run_end(hi / 2, hi, delta_min);
         const u32 j = (u32)((I)i + dir * len);
-        const int delta_node = delta(codes, i, ci, (I)j);
+        const bool j_in = j < n;                             // (a group without a node: any j)
+        const u32 dj = codes.delta(i, ci, (I)j, j_in);
+        const int delta_node = j_in ? (int)dj : -1;
         const I s = run_end((I)0, len, delta_node);
         const u32 gamma = dir > 0 ? (u32)(i + s) : (u32)(i - s - 1);
         if (on && sub == 0) {
-            // the node record's tail, the children's parent words, the links (collision.cl:104-120)
-            const u32 lo = min(i, j), top = max(i, j);
-            const bool a_leaf = lo == gamma, b_leaf = top == gamma + 1;
-            const u32 child_a = a_leaf ? leaf_start + gamma : gamma;
-            const u32 child_b = b_leaf ? leaf_start + gamma + 1 : gamma + 1;
-            if constexpr (NODES) {
-                InnerTail tail = {top, child_a, child_b};
-                *reinterpret_cast<InnerTail *>(&nodes[i].right_edge) = tail;
-                nodes[child_a].parent = i;
-                nodes[child_b].parent = i;
-            }
+            const u32 top = max(i, j);
+            const u32 child_a = node_children<NODES>(nodes, leaf_start, i, j, gamma);
             other_end[i] = j;
             u32 skip = END;
             if (top + 1 < n) {
@@ -729,9 +777,8 @@ __device__ __forceinline__ void search_wave(const u32 *__restrict__ gcodes, col_
                 if (k + 1 >= n) skip = (n - 1) + k;
                 else {
                     // is the right child that starts at leaf k an internal node: its three codes in ONE round trip
-                    const u32 ck = codes.at((I)k), cm = codes.at((I)k - 1), cp = codes.at((I)k + 1);
-                    const u32 d_fwd = min(ffbh_raw(ck ^ cp), 32u + ffbh_raw(k ^ (k + 1u))), d_bwd = min(ffbh_raw(ck ^ cm), 32u + ffbh_raw(k ^ (k - 1u)));
-                    skip = d_fwd > d_bwd ? k : (n - 1) + k;
+                    const u32 ck = codes.at((I)k, true), cm = codes.at((I)k - 1, true), cp = codes.at((I)k + 1, true);
+                    skip = delta_of(k, ck, k + 1u, cp) > delta_of(k, ck, k - 1u, cm) ? k : (n - 1) + k;
                 }
             }
             links_store(bounds, (uint64_t)i, skip, child_a);
@@ -739,160 +786,103 @@ __device__ __forceinline__ void search_wave(const u32 *__restrict__ gcodes, col_
     }
 }
 
-// I: int32_t = the production instance (DPP scans, adjacent deltas, the climb); int64_t = the wide-index instance, which
-// serves n >= 2^30 with shuffle scans and Karras' searches for every node (col_debug_lbvh bit 10: at every size, for tests)
+// The production tree build: 32-bit positions (n < 2^30), DPP scans, adjacent deltas and the climb in LDS.  Its grid is
+// [order_packets workgroups][chunk and search workgroups: PLACES][the bucket report's workgroup]; a chunk workgroup builds the
+// leaves and the in-chunk nodes of one chunk and keeps no code window -- what it reads of the codes are its own 256, one before
+// and two behind.
 // NODES = false: the caller passed no `nodes` array (nothing on the collide path reads it: the walk runs on `bounds`, k_cross
 // on other_end[] of the crossing nodes).  The instance has no store into nodes[] and writes other_end[i] for crossing nodes
 // only -- 5 of a thread's 7 global stores and 36 of the 100 bytes per sphere; bounds, partial, cross and the chunk totals are
-// the same bits.  A compile-time parameter: the nodes-writing instances are instruction for instruction what they were.
-template <typename T, typename I, bool NODES = true>
+// the same bits.
+template <typename T, bool NODES>
 __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, const u32 *__restrict__ ids,
                                              const T *__restrict__ coords, const T *__restrict__ radii,
                                              const T *__restrict__ packed,
                                              col_node *__restrict__ nodes, T *__restrict__ bounds,
                                              u32 *__restrict__ other_end, T *__restrict__ partial, u32 *__restrict__ cross,
                                              T *__restrict__ tab1, u32 n_bound, T block_k, const u32 *__restrict__ n_dev,
-                                             u32 *__restrict__ walk_order = nullptr, int order_mode = 0,
-                                             u32 *report_word = nullptr, u32 report_n = 0) {
-    constexpr bool DPP_SCAN = sizeof(I) == 4, FAST_DELTA = DPP_SCAN, CLIMB = DPP_SCAN;
+                                             u32 *__restrict__ walk_order, int order_mode, u32 *report_word, u32 report_n) {
     const u32 n = count_of(n_bound, n_dev);  // (device-side count, col_common.h: the grid is sized for the bound)
-    typedef typename BT<T>::V4 V4;
-    // (CLIMB: a chunk workgroup keeps no code window -- what it reads of the codes are its own 256, one before and two behind)
-    __shared__ std::conditional_t<CLIMB, ProdLds<T>, ChunkLds<T, false>> lds_mem;
-    __shared__ u32 s_codes_mem[CLIMB ? 1 : WIN];
-    ChunkLds<T, CLIMB> &lds = chunk_lds(lds_mem);
-    u32 *s_codes;
-    if constexpr (CLIMB) s_codes = lds_mem.report; else s_codes = s_codes_mem;
+    __shared__ ProdLds<T> lds_mem;
+    ChunkLds<T> &lds = lds_mem.chunk;
     const int tid = threadIdx.x, lane = tid & (COL_WAVE - 1), w = tid / COL_WAVE;
-    // XCD-aware order: blockIdx % 8 is the XCD (each with its own L2).  Every XCD builds one contiguous run of chunks -- the
-    // same eighth of the sorted leaves whose packets it walks in k_traverse, and neighbouring chunks read overlapping code
-    // windows.  Same bits; whole path, interleaved A/B of two builds on one box: 1 M uniform 0.1706-0.1736 against
-    // 0.1744-0.1757 ms, 2 M 0.293-0.296 against 0.298-0.301, 16 M and config 3 unchanged; a clustered scene at 2 M loses
-    // 2.5 % (the deep chunks of a cluster all go to one XCD; strips of 16 chunks going round the XCDs avoid that and
-    // gain 0.4 % instead of 1.5 %: not taken).
-    // (with a device-side count the grid is sized for the bound: the first `nb` blocks -- dealt round-robin over the XCDs like
-    // all blocks -- share the real chunks, the others leave; with the bound's chunk count in the formula two of eight XCDs sat idle
-    // at a bound of 1.3 n: 70 instead of 51 us)
-    // (CLIMB: with a walk order the first 8 x COL_ORDER_SLICES workgroups of the grid make it -- see order_packets)
-    const u32 nord = CLIMB && walk_order ? 8u * COL_ORDER_SLICES : 0u;
+    // with a walk order the first 8 x COL_ORDER_SLICES workgroups of the grid make it -- see order_packets
+    const u32 nord = walk_order ? 8u * COL_ORDER_SLICES : 0u;
     if (blockIdx.x < nord) {
         order_packets(blockIdx.x, n, n_bound, walk_order, order_mode);
         return;
     }
-    // (CLIMB: the LSD plan's bucket report -- how clustered are the codes, for the caller's next choice of plan -- is the LAST
-    // workgroup of the grid: twenty dependent loads that used to be a launch of their own, 8.8 us on config 3)
-    const u32 nrep = CLIMB && report_word ? 1u : 0u;
-    if (nrep && blockIdx.x == gridDim.x - 1u) {
-        col_bucket_report_block(gcodes, report_n, report_word, s_codes);
+    // the LSD plan's bucket report -- how clustered are the codes, for the caller's next choice of plan -- is the LAST workgroup
+    // of the grid: twenty dependent loads that as a launch of their own take 8.8 us on config 3
+    if (report_word && blockIdx.x == gridDim.x - 1u) {
+        col_bucket_report_block(gcodes, report_n, report_word, lds_mem.report);
         return;
     }
-    // (CLIMB: chunk workgroups and search workgroups share the grid -- PLACES above --, both sized for the bound and, under a
-    // device-side count, clamped the same way: the searchers of chunks at or beyond the real count leave)
+    // Chunk workgroups and search workgroups are both sized for the bound and, under a device-side count, clamped the same way:
+    // the first `nb` chunk workgroups -- dealt round-robin over the XCDs like all workgroups -- share the real chunks, the
+    // others and the searchers of chunks at or beyond the real count leave.  (With the bound's chunk count in xcd_chunk two of
+    // eight XCDs sat idle at a bound of 1.3 n: 70 instead of 51 us.)
     const u32 bound_chunks = (n_bound + (u32)C - 1) / (u32)C;
-    const Place pl = CLIMB ? place_of(blockIdx.x - nord, bound_chunks) : Place{false, blockIdx.x, 0u, 0u};
-    const u32 bid = CLIMB ? pl.bid : blockIdx.x - nord;
-    const u32 nb = n_dev ? (n + (u32)C - 1) / (u32)C : CLIMB ? bound_chunks : gridDim.x - nord - nrep;
-    if constexpr (CLIMB) {
-        if (pl.searcher) {
-            const u32 k = pl.m * SEARCH_CHUNKS + (u32)w, qs = nb / 8, rs = nb % 8, xs = pl.xcd;
-            if (k >= qs + (xs < rs ? 1u : 0u)) return;   // (n == 0 included)
-            search_wave<T, NODES>(gcodes, nodes, bounds, other_end, n, (xs * qs + (xs < rs ? xs : rs) + k) * (u32)C, lds_mem.win[w]);
-            return;
-        }
+    const Place pl = place_of(blockIdx.x - nord, bound_chunks);
+    const u32 nb = n_dev ? (n + (u32)C - 1) / (u32)C : bound_chunks;
+    if (pl.searcher) {
+        const u32 k = pl.m * SEARCH_CHUNKS + (u32)w;
+        if (k >= xcd_chunks(nb, pl.xcd)) return;   // (n == 0 included)
+        search_wave<T, NODES>(gcodes, nodes, bounds, other_end, n, xcd_chunk(nb, pl.xcd, k) * (u32)C, lds_mem.win[w]);
+        return;
     }
-    if (bid >= nb) return;            // (n == 0 included)
-    const u32 q = nb / 8, r = nb % 8, x = bid & 7u;
-    const u32 chunk = x * q + (x < r ? x : r) + (bid >> 3);
+    if (pl.bid >= nb) return;            // (n == 0 included)
+    const u32 chunk = xcd_chunk(nb, pl.bid & 7u, pl.bid >> 3);
     const u32 c0 = chunk * C;
     const u32 p = c0 + tid;
-    Codes<I, FAST_DELTA> codes = {gcodes, (LdsWord *)s_codes, (I)c0 - HALO, n};
     const bool valid = p < n;
-    // Every independent load of the block first -- the three words of the code window and the leaf's id, at clamped
-    // addresses so that none sits behind a branch -- and ONE wait.  As a loop with the LDS store inside, hipcc waited for
-    // each window load before it issued the next: with the id and the row gather five dependent round trips per block,
-    // now two.
-    // (CLIMB: no window -- the leaf's own code alone, with its two neighbours below: three loads instead of five and no 3 KB of
-    // LDS; the searches that probed the window run in the search workgroups)
-    u32 wcode[WIN / C];
-#pragma unroll
-    for (int k = CLIMB ? HALO / C : 0; k < (CLIMB ? HALO / C + 1 : WIN / C); k++) {
-        const I j = codes.w0 + tid + k * C;
-        const bool in = j >= 0 && j < (I)n;
-        const u32 v = gcodes[in ? j : (I)0];
-        wcode[k] = in ? v : 0u;
-    }
+    // Every independent load of the block first -- the leaf's code, its two neighbours, the code behind the chunk and the
+    // leaf's id, at clamped addresses so that none sits behind a branch -- and ONE wait: with the row gather two dependent
+    // round trips per block.
+    // (The signed range test and the two clamps -- the code and, below, the id of a place beyond n are 0 -- are the form this
+    // load has had since it was one step of a window loop; nothing reads the clamped values, but `gcodes[valid ? p : 0u]`
+    // alone, seven instructions less, made col_lbvh 1 us slower at 16 M spheres on each of three boxes: EXPERIMENTS R10.4.)
+    const int32_t jme = (int32_t)c0 + tid;
+    const bool in = jme >= 0 && jme < (int32_t)n;
+    const u32 cme_ld = gcodes[in ? jme : 0];
+    const u32 cme = in ? cme_ld : 0u;
     u32 id = ids[valid ? p : 0u];
-    // Adjacent deltas (FAST_DELTA): delta(p - 1, p) and delta(p, p + 1) from two more coalesced loads issued with the
-    // others.  Karras' direction and delta_min of node p are these two numbers (delta_min is the smaller one: three probes
-    // less), and "is the right child that starts at leaf k an internal node" is adj[k] > adj[k - 1] (right_child_at: a
-    // code read and two probes less, twice per thread) wherever k - 1 and k lie in this chunk.
+    // Adjacent deltas: delta(p - 1, p) and delta(p, p + 1).  Karras' direction of node p is the larger of these two numbers,
+    // and "is the right child that starts at leaf k an internal node" is adj[k] > adj[k - 1] wherever k - 1 and k lie in this
+    // chunk: no code read, no probe.
     int d_prev = -1, d_next = -1;
-    if constexpr (FAST_DELTA && sizeof(I) == 4) {
-        const bool has_prev = valid && p >= 1u, has_next = p + 1u < n;
-        const u32 cprev = gcodes[has_prev ? p - 1u : 0u], cnext = gcodes[has_next ? p + 1u : 0u];
-        const u32 cme = wcode[HALO / C];
-        if (has_prev) d_prev = (int)min(ffbh_raw(cme ^ cprev), 32u + ffbh_raw(p ^ (p - 1u)));
-        if (has_next) d_next = (int)min(ffbh_raw(cme ^ cnext), 32u + ffbh_raw(p ^ (p + 1u)));
-        lds.adj[1 + tid] = (signed char)d_next;
-        if (tid == 0) lds.adj[0] = (signed char)d_prev;
-        // adj[C + 1] = delta(c0 + C, c0 + C + 1): with it "is the right child that starts behind the chunk's last leaf an internal
-        // node" -- the skip link of that leaf and of a node that ends there -- is adj[C + 1] > adj[C] like everywhere else in the
-        // chunk (it was three codes from global memory behind the climb).  One more load, the same address in every lane.
-        const u32 k2 = c0 + (u32)C + 1u;
-        const u32 c2 = gcodes[k2 < n ? k2 : 0u];
-        if (tid == C - 1) lds.adj[C + 1] = k2 < n ? (signed char)min(ffbh_raw(cnext ^ c2), 32u + ffbh_raw((k2 - 1u) ^ k2)) : (signed char)-1;
-    }
-    if constexpr (CLIMB) { if (tid < C / 2) lds.flags[tid] = 0; lds.oe[tid] = (unsigned char)tid; }
-    if constexpr (!CLIMB) {
-#pragma unroll
-        for (int k = 0; k < WIN / C; k++) s_codes[tid + k * C] = wcode[k];
-    }
-    if constexpr (!CLIMB) lds.flags[tid] = 0;
+    const bool has_prev = valid && p >= 1u, has_next = p + 1u < n;
+    const u32 cprev = gcodes[has_prev ? p - 1u : 0u], cnext = gcodes[has_next ? p + 1u : 0u];
+    if (has_prev) d_prev = (int)delta_of(p, cme, p - 1u, cprev);
+    if (has_next) d_next = (int)delta_of(p, cme, p + 1u, cnext);
+    lds.adj[1 + tid] = (signed char)d_next;
+    if (tid == 0) lds.adj[0] = (signed char)d_prev;
+    // adj[C + 1] = delta(c0 + C, c0 + C + 1): with it "is the right child that starts behind the chunk's last leaf an internal
+    // node" -- the skip link of that leaf and of a node that ends there -- is adj[C + 1] > adj[C] like everywhere else in the
+    // chunk.  One more load, the same address in every lane.
+    const u32 k2 = c0 + (u32)C + 1u;
+    const u32 c2 = gcodes[k2 < n ? k2 : 0u];
+    if (tid == C - 1) lds.adj[C + 1] = k2 < n ? (signed char)delta_of(k2 - 1u, cnext, k2, c2) : (signed char)-1;
+    if (tid < C / 2) lds.meet[tid] = 0;
+    lds.oe[tid] = (unsigned char)tid;
     if (tid < (int)CROSS_CAP) cross[(uint64_t)chunk * CROSS_CAP + tid] = END;       // (complete before the barrier below: the fence of __syncthreads)
-    if (tid == 0) { lds.ncross = 0; if constexpr (!CLIMB) lds.flags[C] = 1u; }
+    if (tid == 0) lds.ncross = 0;
     const u32 leaf_start = n - 1;
 
     // leaves: collision.cl:55-63 (fillInternal) + collision.cl:128-141 (leafBounds)
-    Box<T> leaf = box_empty<T>();
     if (!valid) id = 0;
-    if (valid) {
-        const u32 gid = id;
-        V4 c;
-        T r;
-        if (packed) {                 // (x, y, z, r) rows written by col_morton_ex: one gather per leaf
-            c = reinterpret_cast<const V4 *>(packed)[gid];
-            r = c.w;
-        } else {
-            c = reinterpret_cast<const V4 *>(coords)[gid];
-            r = radii[gid];
-        }
-        leaf.lo[0] = c.x - r; leaf.lo[1] = c.y - r; leaf.lo[2] = c.z - r;
-        leaf.hi[0] = c.x + r; leaf.hi[1] = c.y + r; leaf.hi[2] = c.z + r;
-        lds.leaf[0][tid] = c.x; lds.leaf[1][tid] = c.y; lds.leaf[2][tid] = c.z; lds.leaf[3][tid] = r;      // (a place beyond n is never read)
-    }
-
-    // inclusive prefix / suffix unions over the chunk (wave shuffles, then the 4 wave totals)
+    const Box<T> leaf = leaf_in(coords, radii, packed, valid, id, tid, lds.leaf);
+    // inclusive prefix / suffix unions over the chunk: DPP scans in the waves (every lane of the block is still here: full
+    // waves), then the 4 wave totals
     Box<T> pre = leaf, suf = leaf;
-    if constexpr (DPP_SCAN) {          // (every lane of the block is still here: full waves)
-        wave_prefix_union(pre);
-        wave_suffix_union(suf);
-    } else {
-#pragma unroll
-        for (int o = 1; o < COL_WAVE; o <<= 1) {
-            const Box<T> up = box_shfl_up(pre, o), dn = box_shfl_down(suf, o);
-            if (lane >= o) box_merge(pre, up);
-            if (lane + o < COL_WAVE) box_merge(suf, dn);
-        }
-    }
+    wave_prefix_union(pre);
+    wave_suffix_union(suf);
+    // (written out here and in k_chunk_wide: as a function of both boxes hipcc makes ONE store through a selected pointer of
+    // the two, and pre and suf live in scratch -- EXPERIMENTS R10.2)
     if (lane == COL_WAVE - 1) { for (int k = 0; k < 3; k++) { lds.wave_tot[0][w][k] = pre.lo[k]; lds.wave_tot[0][w][3 + k] = pre.hi[k]; } }
     if (lane == 0) { for (int k = 0; k < 3; k++) { lds.wave_tot[1][w][k] = suf.lo[k]; lds.wave_tot[1][w][3 + k] = suf.hi[k]; } }
-    __syncthreads();       // codes window, leaf boxes, ready flags and wave totals are in LDS
-    for (int ww = 0; ww < C / COL_WAVE; ww++) {
-        Box<T> t;
-        for (int k = 0; k < 3; k++) { t.lo[k] = lds.wave_tot[ww < w ? 0 : 1][ww][k]; t.hi[k] = lds.wave_tot[ww < w ? 0 : 1][ww][3 + k]; }
-        if (ww < w) box_merge(pre, t);
-        if (ww > w) box_merge(suf, t);
-    }
+    __syncthreads();       // adjacent deltas, leaf spheres, meeting places and wave totals are in LDS
+    wave_totals_fold(lds.wave_tot, w, pre, suf);
 
     if (valid) {
         if constexpr (NODES) {
@@ -901,137 +891,76 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
         }
         u32 skip_leaf = END;
         if (p + 1 < n) {
-            if constexpr (FAST_DELTA && sizeof(I) == 4) {
-                const u32 k = p + 1;
-                if (k + 1 >= n) skip_leaf = (n - 1) + k;
-                else skip_leaf = lds.adj[tid + 2] > d_next ? k : (n - 1) + k;       // (the chunk's last leaf: adj[C + 1])
-            } else skip_leaf = right_child_at(codes, p + 1);
+            const u32 k = p + 1;
+            if (k + 1 >= n) skip_leaf = (n - 1) + k;
+            else skip_leaf = lds.adj[tid + 2] > d_next ? k : (n - 1) + k;       // (the chunk's last leaf: adj[C + 1])
         }
         record_store(bounds, (uint64_t)leaf_start + p, leaf, skip_leaf, id);
     }
     if (tid == 0)          // chunk total -> level 0 of the first group table
         box_store(tab1, ((uint64_t)(chunk / C) * LV + 0) * C + (chunk % C), suf);
     if (p == n - 1 && n > (u32)C) box_store(partial, p, pre);      // prefix of the last leaf
-    // CLIMB (round 4): the in-chunk nodes bottom-up instead of Karras' searches.  For sorted keys delta(i, j) is the minimum of the
+    // The climb: the in-chunk nodes bottom-up instead of Karras' searches.  For sorted keys delta(i, j) is the minimum of the
     // adjacent deltas between i and j (equal codes included: their deltas 32 + clz(i ^ j) are the common prefix of the keys
     // (code, position)), so the tree is the Cartesian tree of adj[]: a finished range [l, r] is the LEFT child of its parent --
     // Karras' node r -- if delta(r, r + 1) > delta(l - 1, l), else the right child -- node l --, and the two children of the node
     // that splits behind position g meet at meet[g]: the first leaves its far end there and stops, the second takes over the
-    // union and goes on (Apetrei 2014, inside one chunk and in LDS).  One round costs what ONE of the search's probes did, a
-    // thread climbs as far as it arrives second, and the boxes are merged on the way: no search (22 probes per wave), no waiting
-    // for children.  A range whose sibling lies outside the chunk stops; its parent crosses the boundary and is found by the
-    // search below, like every node that the climb has not named (oe[t] == t).
-    if constexpr (CLIMB) {
-        if (valid) {
-            int l = tid, r = tid, my_split = 0;
-            bool is_leaf = true;
-            Box<T> box = leaf;
-            for (;;) {
-                const int dl = lds.adj[l], dr = lds.adj[r + 1];
-                const bool right = dr > dl;
-                if (!is_leaf) {
-                    const int node = right ? r : l;
-                    soa_put(lds.node, node, box);
-                    lds.oe[node] = (unsigned char)(right ? l : r);
-                    lds.split[node] = (unsigned char)my_split;
-                }
-                const int g = right ? r : l - 1;
-                if ((dl & dr) < 0 || g < 0 || g >= C - 1) break;       // the root; or the sibling lies outside the chunk
-                // (LDS instructions of one wave are carried out in order: the box is in lds.node before the exchange, and the reads
-                // below come after it -- the compiler only has to keep that order)
-                asm volatile("" ::: "memory");
-                const u32 place = 16u * ((u32)g & 1u);
-                const u32 old = (__hip_atomic_fetch_or(&lds.flags[g >> 1], ((u32)(right ? l : r) + 1u) << place, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> place) & 0xFFFFu;
-                asm volatile("" ::: "memory");
-                if (old == 0) break;                                    // first: the sibling will take it from here
-                const int far = (int)old - 1;
-                Box<T> sib;
-                if (right) { sib = far == g + 1 ? leaf_get(lds.leaf, g + 1) : soa_get(lds.node, g + 1); r = far; }
-                else { sib = far == g ? leaf_get(lds.leaf, g) : soa_get(lds.node, g); l = far; }
-                box_merge(box, sib);
-                my_split = g;
-                is_leaf = false;
+    // union and goes on (Apetrei 2014, inside one chunk and in LDS).  One round costs what ONE of a search's probes does, a
+    // thread climbs as far as it arrives second, and the boxes are merged on the way: no search, no waiting for children.  A
+    // range whose sibling lies outside the chunk stops; its parent crosses the boundary and is found by the chunk's search
+    // wave, like every node that the climb has not named (oe[t] == t).
+    if (valid) {
+        int l = tid, r = tid, my_split = 0;
+        bool is_leaf = true;
+        Box<T> box = leaf;
+        for (;;) {
+            const int dl = lds.adj[l], dr = lds.adj[r + 1];
+            const bool right = dr > dl;
+            if (!is_leaf) {
+                const int node = right ? r : l;
+                soa_put(lds.node, node, box);
+                lds.oe[node] = (unsigned char)(right ? l : r);
+                lds.split[node] = (unsigned char)my_split;
             }
+            const int g = right ? r : l - 1;
+            if ((dl & dr) < 0 || g < 0 || g >= C - 1) break;       // the root; or the sibling lies outside the chunk
+            // (LDS instructions of one wave are carried out in order: the box is in lds.node before the exchange, and the reads
+            // below come after it -- the compiler only has to keep that order)
+            asm volatile("" ::: "memory");
+            const u32 place = 16u * ((u32)g & 1u);
+            const u32 old = (__hip_atomic_fetch_or(&lds.meet[g >> 1], ((u32)(right ? l : r) + 1u) << place, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> place) & 0xFFFFu;
+            asm volatile("" ::: "memory");
+            if (old == 0) break;                                    // first: the sibling will take it from here
+            const int far = (int)old - 1;
+            Box<T> sib;
+            if (right) { sib = far == g + 1 ? leaf_get(lds.leaf, g + 1) : soa_get(lds.node, g + 1); r = far; }
+            else { sib = far == g ? leaf_get(lds.leaf, g) : soa_get(lds.node, g); l = far; }
+            box_merge(box, sib);
+            my_split = g;
+            is_leaf = false;
         }
-        __syncthreads();
     }
-    // Karras' search (collision.cl:81-121) for node c0 + t: its other end and its split
-    auto search = [&](u32 t, u32 &j, u32 &gamma) {
-        const u32 i = c0 + t, ci = codes.win[HALO + t];       // (= codes.at(i): the chunk's own codes are always in the window)
-        int dir, delta_min;
-        if constexpr (FAST_DELTA && sizeof(I) == 4) {
-            const int dn = lds.adj[t + 1], dp = lds.adj[t];   // delta(i, i + 1), delta(i - 1, i)
-            dir = dn > dp ? 1 : -1;
-            delta_min = min(dn, dp);                           // = delta(i, i - dir)
-        } else {
-            dir = delta(codes, i, ci, (I)i + 1) > delta(codes, i, ci, (I)i - 1) ? 1 : -1;
-            delta_min = delta(codes, i, ci, (I)i - dir);
-        }
-        I len_max = 2;
-        while (delta(codes, i, ci, (I)i + dir * len_max) > delta_min) len_max *= 2;
-        I len = 0;
-        for (I t2 = len_max / 2; t2 > 0; t2 /= 2)
-            if (delta(codes, i, ci, (I)i + dir * (len + t2)) > delta_min) len += t2;
-        j = (u32)((I)i + dir * len);
-        const int delta_node = delta(codes, i, ci, (I)j);
-        I s = 0, t2 = len;
-        do {
-            t2 = (t2 + 1) / 2;
-            if (delta(codes, i, ci, (I)i + dir * (s + t2)) > delta_node) s += t2;
-        } while (t2 > 1);
-        gamma = dir > 0 ? (u32)(i + s) : (u32)(i - s - 1);
-    };
-    // node c0 + t with its other end j and its split: the node record's tail, the children's parent words, the links; returns
-    // the skip link and the left child (collision.cl:104-120).  `crossing`: k_cross will ask for the node's other end (without
-    // NODES nobody else does)
-    auto node_out = [&](u32 t, u32 j, u32 gamma, u32 &skip, u32 &child_a, bool crossing) {
-        const u32 i = c0 + t;
-        const u32 lo = min(i, j), hi = max(i, j);
-        const bool a_leaf = lo == gamma, b_leaf = hi == gamma + 1;
-        child_a = a_leaf ? leaf_start + gamma : gamma;
-        const u32 child_b = b_leaf ? leaf_start + gamma + 1 : gamma + 1;
-        if constexpr (NODES) {
-            InnerTail tail = {hi, child_a, child_b};
-            *reinterpret_cast<InnerTail *>(&nodes[i].right_edge) = tail;
-            nodes[child_a].parent = i;
-            nodes[child_b].parent = i;
-        }
-        // (the wide-index instance keeps every word: it has no oe[] to make up for them in a dense chunk, see crossing_out)
-        if (NODES || !CLIMB || crossing) other_end[i] = j;
-        skip = END;
+    __syncthreads();       // (every thread of the workgroup: `valid` guards the climb, not the barrier)
+    // A node the climb has named: everything is known, and its record goes out.  The others -- three in a hundred: their ranges
+    // cross the chunk's boundary -- leave their half box and their number for k_cross (the direction is in adj[]), and that is
+    // where this workgroup ends: what those nodes still need is Karras' search, which needs nothing this workgroup computes and
+    // whose probes beyond a code window are dependent round trips to global memory (SEARCH WAVE above).
+    if (p >= leaf_start) return;
+    if (lds.oe[tid] != (unsigned char)tid) {
+        const u32 j = c0 + lds.oe[tid], hi = max(p, j);
+        const u32 child_a = node_children<NODES>(nodes, leaf_start, p, j, c0 + lds.split[tid]);
+        if constexpr (NODES) other_end[p] = j;
+        u32 skip = END;
         if (hi + 1 < n) {
-            if constexpr (FAST_DELTA && sizeof(I) == 4) {
-                const u32 k = hi + 1;
-                if (k + 1 >= n) skip = (n - 1) + k;
-                // (a named node's range lies in the chunk: c0 <= hi < c0 + C, and behind its last leaf adj[C + 1] answers)
-                else skip = lds.adj[k - c0 + 1] > lds.adj[hi - c0 + 1] ? k : (n - 1) + k;
-            } else skip = right_child_at(codes, hi + 1);
+            const u32 k = hi + 1;
+            if (k + 1 >= n) skip = (n - 1) + k;
+            // (a named node's range lies in the chunk: c0 <= hi < c0 + C, and behind its last leaf adj[C + 1] answers)
+            else skip = lds.adj[k - c0 + 1] > lds.adj[hi - c0 + 1] ? k : (n - 1) + k;
         }
-    };
-    // a node whose range lies in this chunk: its record with the box, marked as a leaf block if it is small and dense
-    auto record_out = [&](u32 i, u32 j, u32 skip, u32 child_a, const Box<T> &box) {
-        // leaf block (col_common.h): a small DENSE node -- on every axis at most block_k times as wide as its first
-        // leaf -- is marked for the packet walk.  Sparse scenes (BASELINE config 2: leaf boxes a fifth of the
-        // spacing) get no marks and walk as before; where spheres overlap in heaps (config 3) nearly every node
-        // of <= 16 leaves qualifies.
-        const u32 lo = min(i, j), hi = max(i, j);
-        u32 down = child_a;
-        if (hi - lo < COL_LEAF_BLOCK && n <= COL_LEAF_BLOCK_MAX_N && block_k > (T)0) {
-            const Box<T> first = leaf_get(lds.leaf, (int)(lo - c0));
-            bool dense = true;
-#pragma unroll
-            for (int k = 0; k < 3; k++) dense = dense && (box.hi[k] - box.lo[k]) <= block_k * (first.hi[k] - first.lo[k]);
-            if (dense) down = block_link(lo, hi);
-        }
-        record_store(bounds, (uint64_t)i, box, skip, down);
-    };
-    // a node that crosses the chunk's boundary leaves this chunk's half of its range -- the suffix from i (forward) or the prefix up
-    // to i (backward) -- and its number for k_cross
-    auto crossing_out = [&](u32 i, int dir) {
-        box_store(partial, i, dir > 0 ? suf : pre);
-        const u32 slot = atomicAdd(&lds.ncross, 1u);
-        cross[(uint64_t)chunk * CROSS_CAP + (slot < CROSS_CAP - 1 ? slot : CROSS_CAP - 1)] = slot < CROSS_CAP - 1 ? i : CROSS_DENSE;
-        if constexpr (!NODES && CLIMB) {
+        record_out(bounds, lds.leaf, c0, n, block_k, p, j, skip, child_a, soa_get(lds.node, tid));
+    } else {
+        const u32 slot = crossing_out(partial, cross, &lds.ncross, chunk, p, box_select(d_next > d_prev, suf, pre));
+        if constexpr (!NODES) {
             // A dense chunk: k_cross goes through ALL its nodes and tells the crossing ones by other_end[], so the words the
             // named nodes did not write are due after all.  The one thread that finds the list full writes them from oe[]
             // (final since the climb's barrier); a chunk in thousands, on clustered scenes only.
@@ -1040,32 +969,94 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
                 for (u32 t = 0; t < (u32)C && c0 + t < leaf_start; t++)
                     if (lds.oe[t] != (unsigned char)t) other_end[c0 + t] = c0 + lds.oe[t];
         }
-    };
-    if constexpr (CLIMB) {
-        // A node the climb has named: everything is known, and its record goes out.  The others -- three in a hundred: their ranges
-        // cross the chunk's boundary -- leave their half box and their number for k_cross (the direction is in adj[]), and that is
-        // where this workgroup ends.  What those nodes still need is Karras' search, whose probes beyond a code window are dependent
-        // round trips to global memory (with those probes answered "no" the launch was 12 us shorter at 1 M spheres): up to round 7
-        // the waves that had such nodes searched here and held the workgroup's place on the CU meanwhile; the search needs
-        // nothing this workgroup computes and runs in a search workgroup of the same launch (SEARCH WAVE above).
-        // (Measured on the way, with the search in this workgroup: compacted into the lanes of wave 0 behind two barriers: - 1 %; the
-        // same without barriers, after wave 0's own output: + 15 %; 7 places per step in every lane of wave 0: + 9 %.)
-        const bool inner = p < leaf_start;
-        const bool named = inner && lds.oe[tid] != (unsigned char)tid;
-        u32 skip, child_a;
-        if (named) {
-            const u32 j = c0 + lds.oe[tid];
-            node_out((u32)tid, j, c0 + lds.split[tid], skip, child_a, false);
-            record_out(p, j, skip, child_a, soa_get(lds.node, tid));
-        } else if (inner) crossing_out(p, d_next > d_prev ? 1 : -1);
-        return;
     }
+}
+
+// The wide-index tree build: 64-bit positions, for n >= 2^30 (and at every size under col_debug_lbvh bit 10, where the tests
+// use it as a second implementation of k_chunk).  A grid of exactly the chunks' workgroups; each stages a code window, runs
+// Karras' search for every node of its chunk in that node's thread, and waits in LDS until the children of an in-chunk node are
+// final.  k_cross orders the traversal's packets and the bucket report is a launch of its own.  It writes every word of
+// other_end[], with or without NODES: it has no oe[] to make up for them in a dense chunk.
+template <typename T, bool NODES>
+__global__ __launch_bounds__(C) void k_chunk_wide(const u32 *__restrict__ gcodes, const u32 *__restrict__ ids,
+                                                  const T *__restrict__ coords, const T *__restrict__ radii,
+                                                  const T *__restrict__ packed,
+                                                  col_node *__restrict__ nodes, T *__restrict__ bounds,
+                                                  u32 *__restrict__ other_end, T *__restrict__ partial, u32 *__restrict__ cross,
+                                                  T *__restrict__ tab1, u32 n_bound, T block_k, const u32 *__restrict__ n_dev) {
+    typedef int64_t I;      // a (possibly out-of-range) leaf position: i +- 2 * range overflows 32 bits from 2^30 leaves
+    const u32 n = count_of(n_bound, n_dev);
+    __shared__ WideLds<T> lds;
+    const int tid = threadIdx.x, lane = tid & (COL_WAVE - 1), w = tid / COL_WAVE;
+    // (with a device-side count the grid is sized for the bound: the first `nb` workgroups share the real chunks, the others leave)
+    const u32 bid = blockIdx.x, nb = n_dev ? (n + (u32)C - 1) / (u32)C : gridDim.x;
+    if (bid >= nb) return;            // (n == 0 included)
+    const u32 chunk = xcd_chunk(nb, bid & 7u, bid >> 3);
+    const u32 c0 = chunk * C;
+    const u32 p = c0 + tid;
+    const bool valid = p < n;
+    // Every independent load of the block first -- the three words of the code window and the leaf's id, at clamped
+    // addresses so that none sits behind a branch -- and ONE wait.  As a loop with the LDS store inside, hipcc waits for
+    // each window load before it issues the next: with the id and the row gather five dependent round trips per block
+    // instead of two.
+    const I w0 = (I)c0 - HALO;
+    u32 wcode[WIN / C];
+#pragma unroll
+    for (int k = 0; k < WIN / C; k++) {
+        const I j = w0 + tid + k * C;
+        const bool in = j >= 0 && j < (I)n;
+        const u32 v = gcodes[in ? j : (I)0];
+        wcode[k] = in ? v : 0u;
+    }
+    const u32 id = ids[valid ? p : 0u];
+#pragma unroll
+    for (int k = 0; k < WIN / C; k++) lds.win[tid + k * C] = wcode[k];
+    lds.ready[tid] = 0;
+    if (tid < (int)CROSS_CAP) cross[(uint64_t)chunk * CROSS_CAP + tid] = END;       // (complete before the barrier below: the fence of __syncthreads)
+    if (tid == 0) { lds.ncross = 0; lds.ready[C] = 1u; }
+    const u32 leaf_start = n - 1;
+    // code j, 0 <= j < n: from the window, else from global memory
+    LdsWord *win = (LdsWord *)lds.win;
+    const auto code = [=](I j) -> u32 {
+        const I o = j - w0;
+        return (o >= 0 && o < WIN) ? win[o] : gcodes[j];
+    };
+
+    // leaves: collision.cl:55-63 (fillInternal) + collision.cl:128-141 (leafBounds)
+    const Box<T> leaf = leaf_in(coords, radii, packed, valid, id, tid, lds.leaf);
+    // inclusive prefix / suffix unions over the chunk (wave shuffles, then the 4 wave totals)
+    Box<T> pre = leaf, suf = leaf;
+#pragma unroll
+    for (int o = 1; o < COL_WAVE; o <<= 1) {
+        const Box<T> up = box_shfl_up(pre, o), dn = box_shfl_down(suf, o);
+        if (lane >= o) box_merge(pre, up);
+        if (lane + o < COL_WAVE) box_merge(suf, dn);
+    }
+    if (lane == COL_WAVE - 1) { for (int k = 0; k < 3; k++) { lds.wave_tot[0][w][k] = pre.lo[k]; lds.wave_tot[0][w][3 + k] = pre.hi[k]; } }
+    if (lane == 0) { for (int k = 0; k < 3; k++) { lds.wave_tot[1][w][k] = suf.lo[k]; lds.wave_tot[1][w][3 + k] = suf.hi[k]; } }
+    __syncthreads();       // code window, leaf spheres, ready flags and wave totals are in LDS
+    wave_totals_fold(lds.wave_tot, w, pre, suf);
+
+    if (valid) {
+        if constexpr (NODES) {
+            LeafTail tail = {p, id};
+            *reinterpret_cast<LeafTail *>(&nodes[leaf_start + p].right_edge) = tail;
+        }
+        record_store(bounds, (uint64_t)leaf_start + p, leaf, p + 1 < n ? right_child_at(code, n, p + 1) : END, id);
+    }
+    if (tid == 0)          // chunk total -> level 0 of the first group table
+        box_store(tab1, ((uint64_t)(chunk / C) * LV + 0) * C + (chunk % C), suf);
+    if (p == n - 1 && n > (u32)C) box_store(partial, p, pre);      // prefix of the last leaf
     if (p >= leaf_start) return;                      // no barrier below this line
-    u32 j = 0, gamma = 0, skip, child_a;
-    search((u32)tid, j, gamma);
+    // Karras' search (collision.cl:81-121) for node i = c0 + tid: its other end and its split, then the node record's tail,
+    // the children's parent words and the links
     const u32 i = p;
+    u32 j, gamma;
+    karras_search(code, n, i, win[HALO + tid], j, gamma);       // (the chunk's own codes are always in the window)
     const u32 lo = min(i, j), hi = max(i, j);
-    node_out((u32)tid, j, gamma, skip, child_a, !(lo >= c0 && hi < c0 + C));
+    const u32 child_a = node_children<NODES>(nodes, leaf_start, i, j, gamma);
+    other_end[i] = j;
+    const u32 skip = hi + 1 < n ? right_child_at(code, n, hi + 1) : END;
     if (lo >= c0 && hi < c0 + C) {
         // Both children live in this chunk.  Wait (in LDS, workgroup scope) until their boxes are
         // final, merge, publish.  The tree is at most 64 levels deep, so this ends after <= 64
@@ -1076,21 +1067,21 @@ __global__ __launch_bounds__(C) void k_chunk(const u32 *__restrict__ gcodes, con
         const int fa = a_leaf ? C : la, fb = b_leaf ? C : lb;      // both flags are read every round, unconditionally
         for (bool done = false; !done;) {
             // (relaxed loads + ONE acquire fence on success: two acquire loads are two serial LDS round trips per round)
-            const u32 ra = __hip_atomic_load(&lds.flags[fa], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            const u32 rb = __hip_atomic_load(&lds.flags[fb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const u32 ra = __hip_atomic_load(&lds.ready[fa], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            const u32 rb = __hip_atomic_load(&lds.ready[fb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             if (ra & rb) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 box = a_leaf ? leaf_get(lds.leaf, la) : soa_get(lds.node, la);
                 box_merge(box, b_leaf ? leaf_get(lds.leaf, lb) : soa_get(lds.node, lb));
                 soa_put(lds.node, tid, box);
-                __hip_atomic_store(&lds.flags[tid], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_store(&lds.ready[tid], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 done = true;
             }
         }
-        record_out(i, j, skip, child_a, box);
+        record_out(bounds, lds.leaf, c0, n, block_k, i, j, skip, child_a, box);
     } else {
         links_store(bounds, (uint64_t)i, skip, child_a);
-        crossing_out(i, j > i ? 1 : -1);
+        crossing_out(partial, cross, &lds.ncross, chunk, i, box_select(j > i, suf, pre));
     }
 }
 
@@ -1160,10 +1151,7 @@ __device__ __forceinline__ void cross_node(T *__restrict__ bounds, const u32 *__
 // twice (the clamped loads below) cannot change a bit.
 constexpr u32 CROSS_SHORT = 8;                            // a range of at most this many chunks: the slot's own thread reads it
 constexpr u32 CROSS_LIST = (256 / CROSS_CAP) * C;         // longer ranges of a workgroup, at most every node of its 8 chunks
-#ifndef COL_CROSS_DIRECT_MAX_N       /* (-DCOL_CROSS_DIRECT_MAX_N=0: a build that keeps k_group everywhere, for A/Bs of two libraries) */
-#define COL_CROSS_DIRECT_MAX_N COL_MSD_MAX_N
-#endif
-constexpr u32 CROSS_DIRECT_MAX_CHUNKS = COL_CROSS_DIRECT_MAX_N / C;
+constexpr u32 CROSS_DIRECT_MAX_CHUNKS = COL_MSD_MAX_N / C;
 
 // chunk e's total box: level-0 entry e of the first table, [group][level][256]
 __device__ __forceinline__ uint64_t chunk_total_at(u32 e) { return (uint64_t)(e / C) * (LV * C) + e % C; }
@@ -1323,7 +1311,7 @@ __global__ __launch_bounds__(256) void k_cross(T *__restrict__ bounds, const u32
     if (i != END) cross_node(bounds, other_end, partial, tabs, i, lin);
 }
 
-// col_debug_lbvh, process-wide: the wide-index k_chunk at every size / the walk order forced / the tables at every size
+// col_debug_lbvh, process-wide: k_chunk_wide at every size / the walk order forced / the tables at every size
 constexpr int DBG_WIDE = 1024, DBG_ORDER = 4096, DBG_TABLES = 32768;
 int g_dbg = 0;
 float g_block_k = 3.0f;   // leaf-block density criterion (col_debug_leaf_blocks): node width <= k x leaf width; 0 = no marks
@@ -1368,23 +1356,23 @@ int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const 
         // [order_packets workgroups][chunk and search workgroups: PLACES][report workgroup]
         const dim3 grid((walk_order ? 8u * COL_ORDER_SLICES : 0u) + place_blocks(nchunks) + (report_word ? 1u : 0u));
         if (nodes)
-            k_chunk<T, int32_t><<<grid, dim3(C), 0, s>>>(
+            k_chunk<T, true><<<grid, dim3(C), 0, s>>>(
                 codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, n_dev, walk_order, order_mode,
                 report_word, report_n);
         else                            // no Node array asked for: the instance without its stores
-            k_chunk<T, int32_t, false><<<grid, dim3(C), 0, s>>>(
+            k_chunk<T, false><<<grid, dim3(C), 0, s>>>(
                 codes, ids, coords, radii, packed, nullptr, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, n_dev, walk_order, order_mode,
                 report_word, report_n);
         ordered_by_chunk = true;
         report_word = nullptr;          // done in that launch
     } else if (nodes)
-        k_chunk<T, int64_t><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
-                                                               (T *)tabs.t[0], n, (T)g_block_k, n_dev);
+        k_chunk_wide<T, true><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
+                                                                 (T *)tabs.t[0], n, (T)g_block_k, n_dev);
     else
-        k_chunk<T, int64_t, false><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nullptr, bounds, other_end, partial, cross,
-                                                                      (T *)tabs.t[0], n, (T)g_block_k, n_dev);
+        k_chunk_wide<T, false><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nullptr, bounds, other_end, partial, cross,
+                                                                  (T *)tabs.t[0], n, (T)g_block_k, n_dev);
     COL_LAUNCH_OK();
-    if (report_word) {                  // (the wide-index k_chunk has no report workgroup: the report's own launch)
+    if (report_word) {                  // (k_chunk_wide has no report workgroup: the report's own launch)
         const int rc = col_radix_bucket_report((void *)s, codes, report_n, report_word);
         if (rc) return rc;
     }

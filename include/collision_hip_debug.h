@@ -23,7 +23,7 @@ extern "C" {
 int col_debug_xcc_census(void *stream, uint32_t *out, uint32_t nblocks);   /* diagnostics: XCC id per workgroup */
 int col_debug_traverse(int variant);    /* 0 = default; 32768: col_collide's dynamic packet order at every size instead of from
                                          * 400 000 spheres on (tests) */
-int col_debug_lbvh(int mode);           /* 0 = default, or a sum of: 1024: the 64-bit-index instance of the tree build's chunk kernel,
+int col_debug_lbvh(int mode);           /* 0 = default, or a sum of: 1024: k_chunk_wide, the tree build's 64-bit-index chunk kernel,
                                          * which otherwise serves n >= 2^30 only, at every size (tests); 4096: the traversal's
                                          * longest-first walk order whatever the scene (tests); 32768: k_group's tables and
                                          * k_cross's table look-ups at every size, instead of the direct unions up to the MSD size range

@@ -1,7 +1,7 @@
 """The production k_chunk (csrc/lbvh.hip) runs Karras' search for the nodes that cross a chunk boundary in search workgroups
 of its own launch -- a wave per chunk -- while the chunk workgroups end behind the climb; every word of `nodes`, `bounds` and
-other_end[] has exactly one writer.  col_lbvh on constructed sorted codes: the production instance against the wide-index
-instance (col_debug_lbvh bit 1024: the search inside the chunk's workgroup, for every node) byte for byte -- links and marks
+other_end[] has exactly one writer.  col_lbvh on constructed sorted codes: the production kernel against k_chunk_wide
+(col_debug_lbvh bit 1024: the search inside the chunk's workgroup, for every node) byte for byte -- links and marks
 included, on buffers prefilled with 0xFF bytes so that a word nobody wrote cannot pass as a link -- and against the oracle;
 without `nodes` the same `bounds`; and with the count on the device (col_collide_plan_dev under a bound) the arrays and the
 pair set of the exact-n call."""
@@ -20,7 +20,7 @@ from tests.util import assert_same_pair_set, download, pad4, upload
 
 pytestmark = pytest.mark.gpu
 
-WIDE = 1024                 # col_debug_lbvh: the 64-bit-index k_chunk at every size
+WIDE = 1024                 # col_debug_lbvh: k_chunk_wide at every size
 # the root is the only crossing node; either side of two full chunks; ranges that end at the search window's +-256 edge and
 # one leaf beyond it; a range longer than one thread of k_cross reads; far probes across groups of 256 chunks
 SIZES = [257, 511, 512, 513, 769, 1025, 256 * 11 + 1, 256 * 257 + 3]

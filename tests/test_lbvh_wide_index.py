@@ -1,7 +1,7 @@
-"""The 64-bit-index instance of k_chunk (csrc/lbvh.hip) is the only code that builds trees of n >= 2^30 leaves: shuffle
-scans and Karras' searches for every node, where the production instance has DPP scans, adjacent deltas and the climb.
+"""k_chunk_wide, the 64-bit-index chunk kernel (csrc/lbvh.hip), is the only code that builds trees of n >= 2^30 leaves: shuffle
+scans and Karras' searches for every node, where the production k_chunk has DPP scans, adjacent deltas and the climb.
 col_debug_lbvh bit 1024 selects it at every size: col_lbvh on sorted codes must give the oracle's boxes and node records
-bit for bit, and the same bytes -- traversal links and leaf-block marks included -- as the production instance."""
+bit for bit, and the same bytes -- traversal links and leaf-block marks included -- as the production kernel."""
 import numpy as np
 import pytest
 
@@ -10,7 +10,7 @@ from tests.util import pad4, upload
 
 pytestmark = pytest.mark.gpu
 
-WIDE = 1024                 # col_debug_lbvh: the 64-bit-index k_chunk at every size
+WIDE = 1024                 # col_debug_lbvh: k_chunk_wide at every size
 # one chunk, two chunks, a range longer than one thread of k_cross reads (8 whole chunks), two groups of 256 chunks
 SIZES = [2, 257, 256 * 11 + 1, 256 * 257 + 3]
 KINDS = ["uniform", "equal"]

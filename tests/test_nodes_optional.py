@@ -107,7 +107,7 @@ def _crossing_per_chunk(nodes, n):
     return np.bincount(np.arange(n - 1)[cross] // 256, minlength=(n + 255) // 256)
 
 
-WIDE = 1024                              # col_debug_lbvh: the 64-bit-index k_chunk (n >= 2^30) at every size
+WIDE = 1024                              # col_debug_lbvh: k_chunk_wide (n >= 2^30) at every size
 
 
 @pytest.mark.parametrize("mode", [0, WIDE])
@@ -117,7 +117,7 @@ def test_null_nodes_in_a_chunk_with_a_full_crossing_list(hip_env, oracle, n, dt,
     """The instance without Node stores writes other_end[] for crossing nodes only -- except in a chunk whose crossing list
     is full, where k_cross asks for the word of every node.  Scratch prefilled with zeros: a word that was left out would
     read as "my other end is leaf 0", a range that crosses, and the node's finished box would be overwritten.  Also with
-    the wide-index instance, which drops the Node stores alone."""
+    k_chunk_wide, which drops the Node stores alone."""
     ctx, cq = hip_env
     rs = np.random.RandomState(n)
     codes, ids = _two_chains(n), rs.permutation(n).astype(np.uint32)

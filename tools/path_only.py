@@ -35,7 +35,7 @@ if len(sys.argv) > 5:
     lib.col_debug_leaf_blocks(ctypes.c_float(float(sys.argv[5])))
     if len(sys.argv) > 6:
         call.col_debug_traverse(int(sys.argv[6]))
-if os.environ.get("COLLISION_LBVH_MODE"):      # col_debug_lbvh (1024: the wide-index k_chunk; 32768: the table path)
+if os.environ.get("COLLISION_LBVH_MODE"):      # col_debug_lbvh (1024: k_chunk_wide; 32768: the table path)
     from collision_amd._lib import call as _call
     _call.col_debug_lbvh(int(os.environ["COLLISION_LBVH_MODE"]))
 col = Collider(ctx, n, bench.NGROUPS, bench.GROUP_SIZE, coord_dtype=dtype)
