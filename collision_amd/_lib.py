@@ -86,6 +86,10 @@ _PROTOS = {
     "col_collide": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_void_p, C.c_uint32]),
+    "col_collide_batch_max_scene": (C.c_uint32, [C.c_int]),
+    "col_collide_batch_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
+    "col_collide_batch": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "col_partition_scratch_bytes": (C.c_size_t, []),
     "col_partition_sample": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_uint32, C.c_int]),
@@ -143,6 +147,9 @@ _DEBUG_PROTOS = {
     "col_radix_tile_override_active": (C.c_int, []),
 }
 
+# entry points younger than col_version() 100: the version that brought them (a timing run against an older build loads without them)
+_SINCE = {"col_collide_batch_max_scene": 103, "col_collide_batch_scratch_bytes": 103, "col_collide_batch": 103}
+
 EXPORTS = tuple(_PROTOS)
 DEBUG_EXPORTS = tuple(_DEBUG_PROTOS)
 _PROTOS.update(_DEBUG_PROTOS)
@@ -170,9 +177,12 @@ def cdll():
         except Exception:
             pass
     lib = C.CDLL(str(LIB_PATH), mode=C.RTLD_GLOBAL)
+    lib.col_version.restype = C.c_int
     for name, (restype, argtypes) in _PROTOS.items():
         if name in _DEBUG_PROTOS and not hasattr(lib, name):
             continue        # (COLLISION_AMD_LIB: another build of the same ABI; the diagnostics are not part of it and differ by build)
+        if _SINCE.get(name, 0) > lib.col_version() and not hasattr(lib, name):
+            continue        # (COLLISION_AMD_LIB: a build from before this entry point; calling it raises AttributeError)
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int if restype is None else None if restype is _VOID else restype

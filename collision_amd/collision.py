@@ -268,3 +268,78 @@ class Collider:
                 call.col_host_free(word)
             except Exception:
                 pass
+
+
+class BatchCollider:
+    """Many small independent scenes in one call (``col_collide_batch``, csrc/batch.hip): the scenes are concatenated in
+    the caller's arrays, scene s is rows ``[offsets[s], offsets[s + 1])``, and every scene gets exactly the result
+    ``Collider.get_collisions`` gives for it alone -- in 2 launches whatever the number of scenes, instead of a loop of
+    6 launches per scene.  ``max_scene`` bounds a scene's size (it chooses the kernel instance, never a result); a scene
+    beyond it is skipped and reads ``SKIPPED`` in ``scene_counts_buf``."""
+    counter_dtype = np.dtype("uint32")
+    id_dtype = np.dtype("uint32")
+    code_dtype = np.dtype("uint32")
+    SKIPPED = 0xFFFFFFFF                # COL_BATCH_SKIPPED
+
+    def __init__(self, ctx, total_size, n_scenes, max_scene, coord_dtype=np.dtype("float32"), program=None,
+                 keep_sorted=False):
+        coord_dtype = np.dtype(coord_dtype)
+        if program is None:
+            program = CollisionProgram(ctx, coord_dtype)
+        else:
+            if program.context != ctx:
+                raise ValueError("Collider and program context must match")
+            if program.coord_dtype != coord_dtype:
+                raise ValueError("Collider and program coord_dtype must match")
+        self.program = program
+        self.keep_sorted = bool(keep_sorted)
+        self._alloc = {}
+        self.total_size, self.n_scenes, self.max_scene = 0, 0, 1
+        self.resize(total_size, n_scenes, max_scene)
+
+    @property
+    def max_scene_limit(self):
+        return int(call.col_collide_batch_max_scene(self.program.coord_dtype.itemsize))
+
+    def resize(self, total_size=None, n_scenes=None, max_scene=None):
+        if max_scene is not None:
+            if not 1 <= max_scene <= self.max_scene_limit:
+                raise ValueError("Invalid max_scene: {} (1 .. {})".format(max_scene, self.max_scene_limit))
+            self.max_scene = int(max_scene)
+        if total_size is not None:
+            self.total_size = int(total_size)
+        if n_scenes is not None:
+            self.n_scenes = int(n_scenes)
+        self._allocate()
+
+    def _allocate(self):
+        """(Re)allocate only what changed size: the scratch, and with keep_sorted the sorted codes / local ids."""
+        want = {"scratch": call.col_collide_batch_scratch_bytes(self.n_scenes, self.total_size, self.max_scene,
+                                                                self.program.coord_dtype.itemsize)}
+        if self.keep_sorted:
+            want["codes"] = want["ids"] = max(self.total_size, 1) * 4
+        for name, nbytes in want.items():
+            if nbytes and (name not in self._alloc or self._alloc[name].size != nbytes):
+                self._alloc[name] = hip.Buffer(self.program.context, nbytes)
+            elif not nbytes:
+                self._alloc.pop(name, None)
+        self._codes_buf = self._alloc.get("codes") if self.keep_sorted else None
+        self._ids_buf = self._alloc.get("ids") if self.keep_sorted else None
+
+    def get_collisions(self, cq, coords_buf, radii_buf, offsets_buf, n_collisions_buf, scene_counts_buf, collisions_buf,
+                       n_collisions, wait_for=None):
+        """Enqueue the batch.  offsets_buf: n_scenes + 1 uint32 on the device.  n_collisions_buf (1 uint32) receives the
+        TOTAL number of overlapping pairs over all scenes, scene_counts_buf (n_scenes uint32) every scene's own count;
+        the first ``n_collisions`` pairs are written to collisions_buf as rows of global row indices, in no particular
+        order.  collisions_buf may be None when n_collisions == 0 (count-only mode)."""
+        if collisions_buf is None and n_collisions > 0:
+            raise ValueError("Invalid collisions_buf for n_collisions > 0")
+        cq.wait_for(wait_for)
+        scratch = self._alloc.get("scratch")
+        call.col_collide_batch(
+            cq.stream, coords_buf.ptr, radii_buf.ptr, offsets_buf.ptr, self.n_scenes, self.total_size, self.max_scene,
+            self.program.coord_dtype.itemsize,
+            None if self._codes_buf is None else self._codes_buf.ptr, None if self._ids_buf is None else self._ids_buf.ptr,
+            None if scratch is None else scratch.ptr, n_collisions_buf.ptr, scene_counts_buf.ptr,
+            None if collisions_buf is None else collisions_buf.ptr, n_collisions)
+        return hip.Event(cq)

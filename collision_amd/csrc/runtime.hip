@@ -49,7 +49,8 @@ const char *col_error_string(int code) {
 
 // 101: `nodes` may be NULL in col_lbvh and the col_collide family
 // 102: col_collide's intermediates codes0 / ids0 hold digit-sorted tiles on the MSD plan below 1 Mi codes (include/collision_hip.h)
-int col_version(void) { return 102; }
+// 103: col_collide_batch (csrc/batch.hip)
+int col_version(void) { return 103; }
 
 int col_device_count(int *count) { COL_HIP(hipGetDeviceCount(count)); return COL_OK; }
 int col_set_device(int device) { COL_HIP(hipSetDevice(device)); return COL_OK; }

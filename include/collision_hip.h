@@ -292,6 +292,34 @@ int col_collide_plan_dev(void *stream, const void *coords, const void *radii, ui
                          uint32_t *collisions, uint32_t capacity, int sort_plan, uint32_t *oversize,
                          const void *partials, uint32_t parts, const uint32_t *n_dev);
 
+/* ---------------------------------------------------------------- batched path (col_version() >= 103)
+ * Many small independent scenes in one call: scene s is rows [offsets[s], offsets[s+1]) of `coords` (`total` rows of
+ * 4 scalars, lane w ignored) and `radii` (`total` scalars); `offsets` is DEVICE memory, n_scenes + 1 words; empty scenes
+ * are allowed.  Scene s gets exactly what col_collide gives for that scene alone (its own scene bounds, codes, stable
+ * sort and pairs).  One workgroup holds a scene (several small ones) in LDS from the bounds to the pairs: 2 launches
+ * whatever n_scenes is (the counter's memset and the kernel; csrc/batch.hip).
+ *   max_scene     the host's bound on a scene's size, 1 .. col_collide_batch_max_scene(coord_bytes); it picks the kernel
+ *                 instance (scenes of at most 64 / 256 / 512 / 1024 spheres) and changes no result.
+ *   counter[0]    total number of hits over all scenes (counts past `capacity`, as col_traverse does).
+ *   scene_counts  n_scenes words: the hit count of scene s, independent of `capacity`; COL_BATCH_SKIPPED for a scene
+ *                 whose size (as an unsigned difference) exceeds max_scene or whose end exceeds `total` (so for
+ *                 non-monotone offsets too): such a scene contributes nothing anywhere and affects no other scene.
+ *   pairs         the first `capacity` hits as rows of GLOBAL row indices (offsets[s] + id[q], offsets[s] + id[p]), q
+ *                 before p in the scene's stably sorted order, in no particular order; may be NULL when capacity == 0.
+ *   codes_out, ids_out   (each may be NULL) `total` words: the scene's sorted codes and sorted LOCAL ids at
+ *                 [offsets[s], offsets[s+1]).
+ * The call zeroes counter and scene_counts itself, on the stream.  n_scenes == 0: COL_OK, nothing is launched.
+ * COL_EINVAL (before any HIP call): coord_bytes not 4 | 8, max_scene == 0 or above the limit, pairs == NULL with
+ * capacity > 0, counter / scene_counts / offsets NULL.  col_collide_batch_max_scene: 0 for any other coord_bytes.
+ * col_collide_batch_scratch_bytes may be 0 (`scratch` may then be NULL); it is monotone in its size arguments. */
+#define COL_BATCH_SKIPPED 0xFFFFFFFFu
+uint32_t col_collide_batch_max_scene(int coord_bytes);
+size_t col_collide_batch_scratch_bytes(uint32_t n_scenes, uint32_t total, uint32_t max_scene, int coord_bytes);
+int col_collide_batch(void *stream, const void *coords, const void *radii, const uint32_t *offsets,
+                      uint32_t n_scenes, uint32_t total, uint32_t max_scene, int coord_bytes,
+                      uint32_t *codes_out, uint32_t *ids_out, void *scratch,
+                      uint32_t *counter, uint32_t *scene_counts, uint32_t *pairs, uint32_t capacity);
+
 /* ---------------------------------------------------------------- multi-GPU helpers
  * New work (the reference is single-device): device side of the sphere
  * repartition / halo exchange / ghost queries driven by collision_amd/multi.py over RCCL.
