@@ -961,6 +961,9 @@ static bool asm_walk_ok(const void *bounds, uint32_t n, size_t coord_bytes) {
     return (2ull * n - 1) * 8 * coord_bytes < (1ull << 32) && ((uintptr_t)bounds & 63) == 0;
 }
 
+// the walks' grid for `nqueries` queries in packets of 64: 2 resident blocks of 16 waves per CU, grid-stride beyond
+static u32 traverse_grid(u32 nqueries) { const u32 b = (u32)col_ceil_div((nqueries + 63) / 64, TW); return b > 512 ? 512 : b; }
+
 // Packet walk vs a lane-per-query walk, measured on MI355X at 1 M spheres: 0.109 vs 0.120 ms on the uniform scene, 0.78 vs
 // 1.04 ms on a clustered one (11 M pairs).  Halving the resident waves costs +35 %: about a third of the walk is exposed
 // latency of its dependent record loads at the hardware's 8 waves/SIMD, the rest is instruction issue.
@@ -970,10 +973,7 @@ template <typename T>
 int launch_traverse(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const void *bounds,
                     uint32_t n, uint64_t *stats, int mode, uint32_t *sched = nullptr, const uint32_t *n_dev = nullptr,
                     uint32_t *walk_order = nullptr) {
-    const u32 npackets = (n + 63) / 64;
-    u32 blocks = (u32)col_ceil_div(npackets, TW);
-    if (blocks > 512) blocks = 512;               // 2 resident blocks of 16 waves per CU, grid-stride beyond
-    dim3 g(blocks), t(TT);
+    dim3 g(traverse_grid(n)), t(TT);
     hipStream_t s = col_stream(stream);
     const T *bd = (const T *)bounds;
     if (stats) {
@@ -1105,13 +1105,10 @@ __global__ __launch_bounds__(256) void k_pairs_compact(u32 *__restrict__ pairs, 
 // (the list could then not be closed and is rebuilt the exact way: still min(count, capacity) valid pairs).
 template <typename T>
 int launch_traverse_chunked(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const void *bounds,
-                            uint32_t n, void *scratch, const uint32_t *n_dev = nullptr, uint32_t *walk_order = nullptr,
-                            bool hdr_cleared = false) {
+                            uint32_t n, void *scratch, const uint32_t *n_dev, uint32_t *walk_order, bool hdr_cleared) {
     // (dynamic packet order, its counters in the header's pad: always -- a dense scene's packets differ by 5 x in time)
     const int dyn = n <= COL_SPLIT_UNITS_UPTO ? 256 | 512 : 256;
-    const u32 npackets = (n + 63) / 64;
-    u32 blocks = (u32)col_ceil_div(npackets, TW);
-    if (blocks > 512) blocks = 512;
+    const u32 blocks = traverse_grid(n);
     dim3 g(blocks), t(TT);
     hipStream_t s = col_stream(stream);
     const T *bd = (const T *)bounds;
@@ -1131,9 +1128,7 @@ int launch_traverse_chunked(void *stream, uint32_t *pairs, uint32_t *counter, ui
 template <typename T>
 int launch_ghost(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const void *bounds, uint32_t n,
                  const GhostArgs &ga, uint32_t max_ghosts, const uint32_t *n_dev) {
-    const u32 npackets = (max_ghosts + 63) / 64;
-    u32 blocks = (u32)col_ceil_div(npackets, TW);
-    if (blocks > 512) blocks = 512;
+    const u32 blocks = traverse_grid(max_ghosts);
     if (blocks == 0) return COL_OK;
     dim3 g(blocks), t(TT);
     hipStream_t s = col_stream(stream);
@@ -1158,6 +1153,28 @@ extern "C" int col_traverse_ghost_packets(void *stream, uint32_t *pairs, uint32_
     if (coord_bytes == 8) return launch_ghost<double>(stream, pairs, counter, capacity, bounds, n, ga, max_ghosts, n_dev);
     return COL_EINVAL;
 }
+
+// The whole path's walks (collide.hip; col_common.h).  The exact one: the caller has checked n and coord_bytes.
+extern "C" int col_traverse_walk(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const void *bounds,
+                                 uint32_t n, int coord_bytes, uint32_t *sched, const uint32_t *n_dev, uint32_t *walk_order) {
+    if (coord_bytes == 4) return launch_traverse<float>(stream, pairs, counter, capacity, bounds, n, nullptr, 0, sched, n_dev, walk_order);
+    return launch_traverse<double>(stream, pairs, counter, capacity, bounds, n, nullptr, 0, sched, n_dev, walk_order);
+}
+
+// col_traverse_chunked with a device-side count, a walk order and (hdr_cleared) a header that an earlier launch has cleared
+extern "C" int col_traverse_chunked_walk(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const void *bounds,
+                                         uint32_t n, int coord_bytes, void *scratch, const uint32_t *n_dev, uint32_t *walk_order,
+                                         int hdr_cleared) {
+    if (n < 2) return COL_OK;
+    if ((capacity > 0 && !pairs) || (coord_bytes != 4 && coord_bytes != 8)) return COL_EINVAL;
+    if (!scratch || !asm_walk_ok(bounds, n, (size_t)coord_bytes))
+        return col_traverse_walk(stream, pairs, counter, capacity, bounds, n, coord_bytes, nullptr, n_dev, nullptr);
+    if (coord_bytes == 8) return launch_traverse_chunked<double>(stream, pairs, counter, capacity, bounds, n, scratch, n_dev, walk_order, hdr_cleared != 0);      // (round 4: the asm walk has a float64 form)
+    return launch_traverse_chunked<float>(stream, pairs, counter, capacity, bounds, n, scratch, n_dev, walk_order, hdr_cleared != 0);
+}
+
+// (col_debug_traverse's bit: at every size, so that the small parity cases of tests/ take the dynamic order too)
+extern "C" int col_traverse_dynamic_order(uint32_t n) { return n >= COL_DYNAMIC_PACKETS_FROM || (g_traverse_variant & 32768) ? 1 : 0; }
 
 extern "C" {
 
@@ -1212,10 +1229,8 @@ int col_traverse(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capa
                  const void *bounds, uint32_t n, int coord_bytes) {
     (void)nodes;   // the traversal runs on the 32-byte records in `bounds` alone
     if (n < 2) return COL_OK;
-    if (capacity > 0 && !pairs) return COL_EINVAL;
-    if (coord_bytes == 4) return launch_traverse<float>(stream, pairs, counter, capacity, bounds, n, nullptr, 0);
-    if (coord_bytes == 8) return launch_traverse<double>(stream, pairs, counter, capacity, bounds, n, nullptr, 0);
-    return COL_EINVAL;
+    if ((capacity > 0 && !pairs) || (coord_bytes != 4 && coord_bytes != 8)) return COL_EINVAL;
+    return col_traverse_walk(stream, pairs, counter, capacity, bounds, n, coord_bytes, nullptr, nullptr, nullptr);
 }
 
 size_t col_traverse_chunked_scratch_bytes(void) { return sizeof(ChunkHdr); }
@@ -1224,27 +1239,9 @@ size_t col_traverse_chunked_scratch_bytes(void) { return sizeof(ChunkHdr); }
 // 8192 pairs (one atomic on the counter per chunk instead of one per 512 pairs) and a small kernel closes the holes at
 // the end.  *counter must be 0 on entry (the list starts here).  Record arrays below 4 GB and 64-byte aligned (what the
 // asm walks need); anything else takes col_traverse.  scratch: col_traverse_chunked_scratch_bytes().
-static int traverse_chunked_dev(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const col_node *nodes,
-                                const void *bounds, uint32_t n, int coord_bytes, void *scratch, const uint32_t *n_dev,
-                                uint32_t *walk_order = nullptr, bool hdr_cleared = false);
-int col_traverse_chunked(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const col_node *nodes,
+int col_traverse_chunked(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const col_node *,
                          const void *bounds, uint32_t n, int coord_bytes, void *scratch) {
-    return traverse_chunked_dev(stream, pairs, counter, capacity, nodes, bounds, n, coord_bytes, scratch, nullptr);
-}
-static int traverse_chunked_dev(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const col_node *nodes,
-                                const void *bounds, uint32_t n, int coord_bytes, void *scratch, const uint32_t *n_dev,
-                                uint32_t *walk_order, bool hdr_cleared) {
-    if ((coord_bytes != 4 && coord_bytes != 8) || !scratch || !asm_walk_ok(bounds, n, (size_t)coord_bytes)) {
-        if (n < 2) return COL_OK;
-        if (capacity > 0 && !pairs) return COL_EINVAL;
-        if (coord_bytes == 4) return launch_traverse<float>(stream, pairs, counter, capacity, bounds, n, nullptr, 0, nullptr, n_dev);
-        if (coord_bytes == 8) return launch_traverse<double>(stream, pairs, counter, capacity, bounds, n, nullptr, 0, nullptr, n_dev);
-        return COL_EINVAL;
-    }
-    if (n < 2) return COL_OK;
-    if (capacity > 0 && !pairs) return COL_EINVAL;
-    if (coord_bytes == 8) return launch_traverse_chunked<double>(stream, pairs, counter, capacity, bounds, n, scratch, n_dev, walk_order, hdr_cleared);      // (round 4: the asm walk has a float64 form)
-    return launch_traverse_chunked<float>(stream, pairs, counter, capacity, bounds, n, scratch, n_dev, walk_order, hdr_cleared);
+    return col_traverse_chunked_walk(stream, pairs, counter, capacity, bounds, n, coord_bytes, scratch, nullptr, nullptr, 0);
 }
 
 // Diagnostics: same traversal, also accumulates stats[0..7] (8 x u64) = phase-2 steps, descents, leaf
@@ -1255,131 +1252,6 @@ int col_traverse_stats(void *stream, uint32_t *pairs, uint32_t *counter, uint32_
     if (coord_bytes == 4) return launch_traverse<float>(stream, pairs, counter, capacity, bounds, n, stats, mode);
     if (coord_bytes == 8) return launch_traverse<double>(stream, pairs, counter, capacity, bounds, n, stats, mode);
     return COL_EINVAL;
-}
-
-size_t col_collide_scratch_bytes(uint32_t n, uint32_t padded, int coord_bytes) {
-    return 256 /* scene range */ + col_reduce_scratch_bytes(coord_bytes == 8 ? COL_F64 : COL_F32, 4) +
-           col_radix_scratch_bytes(padded, 4, 4) + col_lbvh_scratch_bytes(n, coord_bytes) +
-           (size_t)n * 4 * coord_bytes /* packed (x,y,z,r) rows */ + sizeof(ChunkHdr) + 256 /* chunked pair allocation */ + 1024 +
-           8 * ((size_t)n / 64 + 1) + 256 /* walk order: cost[] + perm[] */ +
-           256 + col_radix_msd_fused_bytes() /* the MSD pass without a scan launch: group sums + bucket starts */;
-}
-
-int col_collide(void *stream, const void *coords, const void *radii, uint32_t n, uint32_t padded, int coord_bytes,
-                uint32_t *codes0, uint32_t *codes1, uint32_t *ids0, uint32_t *ids1, col_node *nodes, void *bounds,
-                uint32_t *flags, void *scratch, uint32_t *counter, uint32_t *pairs, uint32_t capacity) {
-    return col_collide_plan(stream, coords, radii, n, padded, coord_bytes, codes0, codes1, ids0, ids1, nodes, bounds, flags,
-                            scratch, counter, pairs, capacity, COL_SORT_LSD, nullptr);
-}
-
-int col_collide_plan(void *stream, const void *coords, const void *radii, uint32_t n, uint32_t padded, int coord_bytes,
-                     uint32_t *codes0, uint32_t *codes1, uint32_t *ids0, uint32_t *ids1, col_node *nodes, void *bounds,
-                     uint32_t *flags, void *scratch, uint32_t *counter, uint32_t *pairs, uint32_t capacity,
-                     int sort_plan, uint32_t *oversize) {
-    return col_collide_plan_partials(stream, coords, radii, n, padded, coord_bytes, codes0, codes1, ids0, ids1, nodes, bounds,
-                                     flags, scratch, counter, pairs, capacity, sort_plan, oversize, nullptr, 0);
-}
-
-// col_collide_plan with the bounds partials of `coords` already computed (col_minmax4_stage1 / _dev: `parts` records of
-// [min row, max row] at `partials`; NULL = compute them here).  The fused front end applies at every size of a (u32, u32) sort;
-// only the unfused fallback below (a tile class it does not know) ignores the partials.
-int col_collide_plan_partials(void *stream, const void *coords, const void *radii, uint32_t n, uint32_t padded, int coord_bytes,
-                              uint32_t *codes0, uint32_t *codes1, uint32_t *ids0, uint32_t *ids1, col_node *nodes, void *bounds,
-                              uint32_t *flags, void *scratch, uint32_t *counter, uint32_t *pairs, uint32_t capacity,
-                              int sort_plan, uint32_t *oversize, const void *partials, uint32_t parts) {
-    return col_collide_plan_dev(stream, coords, radii, n, padded, coord_bytes, codes0, codes1, ids0, ids1, nodes, bounds, flags, scratch,
-                                counter, pairs, capacity, sort_plan, oversize, partials, parts, nullptr);
-}
-
-// The whole path with the number of spheres ON THE DEVICE (include/collision_hip.h): n is a host-known bound that sizes grids,
-// scratch and the sort (rows from *n_dev on become pads), every kernel works on min(n, *n_dev).  Needs the bounds partials
-// (col_minmax4_stage1_dev reads the same word).
-int col_collide_plan_dev(void *stream, const void *coords, const void *radii, uint32_t n, uint32_t padded, int coord_bytes,
-                         uint32_t *codes0, uint32_t *codes1, uint32_t *ids0, uint32_t *ids1, col_node *nodes, void *bounds,
-                         uint32_t *flags, void *scratch, uint32_t *counter, uint32_t *pairs, uint32_t capacity,
-                         int sort_plan, uint32_t *oversize, const void *partials, uint32_t parts, const uint32_t *n_dev) {
-    if (coord_bytes != 4 && coord_bytes != 8) return COL_EINVAL;
-    if (n_dev && !partials) return COL_EINVAL;
-    if (partials && (parts == 0 || parts > COL_MINMAX_PARTS)) return COL_EINVAL;
-    if (padded < n || (capacity > 0 && !pairs)) return COL_EINVAL;
-    if (!scratch) return COL_ENOSCRATCH;
-    // a forced radix tile class (diagnostics) would not match the histogram the fused Morton kernel writes
-    if (col_radix_tile_override_active()) return COL_EINVAL;
-    hipStream_t s = col_stream(stream);
-    if (n == 0) {
-        COL_HIP(hipMemsetAsync(counter, 0, sizeof(uint32_t), s));             // collision.py:151-154
-        return COL_OK;
-    }
-    (void)flags;   // the arrival counters of internalBounds (collision.py:147-150) are not needed: see lbvh.hip
-    char *p = (char *)scratch;
-    void *range = p;           p += 256;
-    void *red_scratch = p;     p += col_reduce_scratch_bytes(coord_bytes == 8 ? COL_F64 : COL_F32, 4);
-    p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-    void *sort_scratch = p;    p += col_radix_scratch_bytes(padded, 4, 4);
-    p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-    void *lbvh_scratch = p;    p += col_lbvh_scratch_bytes(n, coord_bytes);
-    p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-    void *packed = p;          p += (size_t)n * 4 * coord_bytes;
-    p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-    void *chunk_hdr = p;       p += sizeof(ChunkHdr) + 256 + 8 * ((size_t)n / 64 + 1) + 256;     // header, packet counters, walk order
-    p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-    uint32_t *msd_fused = (uint32_t *)p;       // group sums (zero before the Morton kernel, in every call) + bucket starts
-    // sort_plan: bit 0 = the sort (COL_SORT_LSD / COL_SORT_MSD), bit 1 = COL_TRAVERSE_CHUNKED (dense scenes)
-    const bool chunked = (sort_plan & COL_TRAVERSE_CHUNKED) != 0;
-    sort_plan &= 1;
-    uint32_t *publish = oversize ? oversize + 2 : nullptr;      // the previous call's pair count, for the caller's next choice
-    int rc;
-    uint32_t *report_word = nullptr;      // the LSD plan's bucket report rides in the tree build's first launch (lbvh.hip)
-    const uint32_t tile = col_radix_tile(padded, 4, 4);
-    if (tile == 1024 || tile == 4096 || tile == 8192) {
-        // The front end is fused (every tile class of a (u32, u32) sort): the Morton kernel folds the bounds partials itself and
-        // counts the digits of the sort's first pass (the histogram sits at the start of the sort scratch): two
-        // launches less.  The MSD plan (one global pass + an LDS finish per bucket) applies up to COL_MSD_MAX_N.
-        const bool msd = sort_plan == COL_SORT_MSD && padded <= COL_MSD_MAX_N;
-        // MSD: no scan launch either -- the Morton kernel also adds its counts into group sums and the pass works out its own
-        // offsets (radix.hip, k_scatter FUSED).  The group sums are cleared by the bounds kernel when it runs here, else by a memset.
-        // The 1024-pair tile class (round 9) has no global pass at all: the Morton kernel leaves every tile sorted by the bucket digit
-        // with a table of (start, count) words, and each bucket's workgroup gathers its pieces itself (radix.hip, k_bucket_sort GATHER).
-        const bool gather = msd && tile == 1024;
-        const uint32_t mtile = gather && padded >= COL_GATHER_BIG_FROM ? 4096u : tile;      // the Morton kernel's tile (col_common.h)
-        const uint32_t nsums = msd ? (uint32_t)(col_radix_msd_fused_bytes() / sizeof(uint32_t)) : 0u;
-        if (msd && col_ceil_div(padded, tile) > (uint64_t)COL_MSD_GROUP * COL_MSD_GROUPS) return COL_EINVAL;    // (more tiles than group sums: no tile class does that)
-        if (!partials) {
-            if ((rc = col_minmax4_stage1_zero(stream, coords, n, coord_bytes, red_scratch, &parts, msd_fused, nsums))) return rc;
-            partials = red_scratch;
-        } else if (msd)
-            COL_HIP(hipMemsetAsync(msd_fused, 0, nsums * sizeof(uint32_t), s));
-        if ((rc = col_morton_tile(stream, coords, radii, partials, parts, n, padded, coord_bytes, codes0, ids0, packed,
-                                  counter, (uint32_t *)sort_scratch, mtile, (uint32_t)col_ceil_div(padded, mtile), msd ? 22 : 0,
-                                  publish, n_dev, msd ? msd_fused : nullptr, gather ? 1 : 0))) return rc;
-        if (gather) rc = col_radix_sort_msd_gather(stream, codes0, codes1, ids0, ids1, n, padded, sort_scratch, oversize, n_dev, msd_fused, mtile);
-        else if (msd) rc = col_radix_sort_msd_fused(stream, codes0, codes1, ids0, ids1, padded, sort_scratch, oversize, n_dev, msd_fused);
-        else rc = col_radix_sort_ex(stream, codes0, codes1, ids0, ids1, padded, 4, 4, sort_scratch, 0, 1);
-        if (rc) return rc;
-        // the LSD plan was taken where the MSD plan could apply: tell the caller how clustered the codes are (oversize[1])
-        if (!msd && oversize && padded <= COL_MSD_MAX_N) report_word = oversize + 1;
-    } else {
-        if (n_dev) return COL_EINVAL;            // (a forced tile class: diagnostics only)
-        if ((rc = col_reduce(stream, coords, n, coord_bytes == 8 ? COL_F64 : COL_F32, 4, COL_OP_MINMAX, red_scratch, range))) return rc;
-        if ((rc = col_morton_ex(stream, coords, radii, range, n, padded, coord_bytes, codes0, ids0, packed, counter, publish))) return rc;
-        if ((rc = col_radix_sort(stream, codes0, codes1, ids0, ids1, padded, 4, 4, sort_scratch, 0))) return rc;
-    }
-    // the traversal's packet counters (dynamic packet order, k_traverse): cleared by the tree build's last kernel
-    // (variant bit 15: from any size, so that the small parity cases of tests/ take this way too)
-    uint32_t *sched = (!chunked && (n >= COL_DYNAMIC_PACKETS_FROM || (g_traverse_variant & 32768))) ? (uint32_t *)((char *)chunk_hdr + sizeof(ChunkHdr)) : nullptr;
-    // the walk order (col_common.h): cost[] and perm[] behind the chunk header, wherever the dynamic packet order runs and the tree
-    // build ends with k_cross (more than one chunk)
-    // WALK ORDER (col_common.h): a dense scene orders its walks longest first, a sparse one of up to COL_DEAL_MAX_N spheres deals its
-    // long walks over the first round; larger sparse scenes record and order nothing
-    const int order_mode = chunked || col_lbvh_order_forced() ? 1 : 0;
-    uint32_t *walk_order = n > 256 && (chunked || (sched && (n <= COL_DEAL_MAX_N || order_mode))) ? (uint32_t *)((char *)chunk_hdr + sizeof(ChunkHdr) + 256) : nullptr;
-    // (chunked: the tree build's last kernel clears the walk's whole 64-byte header -- its memset was a launch of 4.8 us)
-    if ((rc = col_lbvh_ex(stream, codes1, ids1, coords, radii, packed, nodes, bounds, lbvh_scratch, n, coord_bytes,
-                          chunked ? (uint32_t *)chunk_hdr : sched, n_dev, walk_order, order_mode, chunked ? 16u : 8u, report_word, padded))) return rc;
-    if (chunked) return traverse_chunked_dev(stream, pairs, counter, capacity, nodes, bounds, n, coord_bytes, chunk_hdr, n_dev, walk_order, true);
-    if (n < 2) return COL_OK;
-    if (coord_bytes == 4) return launch_traverse<float>(stream, pairs, counter, capacity, bounds, n, nullptr, 0, sched, n_dev, walk_order);
-    return launch_traverse<double>(stream, pairs, counter, capacity, bounds, n, nullptr, 0, sched, n_dev, walk_order);
 }
 
 }  // extern "C"

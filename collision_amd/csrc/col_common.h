@@ -20,77 +20,87 @@
         if (e_ != hipSuccess) return (int)e_;          \
     } while (0)
 
-// internal entry points shared between translation units (not part of the public header)
+// ---- constants shared between translation units ----
+#define COL_MINMAX_PARTS 256    // col_minmax4_stage1_zero / _dev leave at most this many partial results
+// col_radix_sort_msd: one workgroup finishes one of 256 top-digit buckets in LDS -- 8192 pairs per bucket for
+// inputs up to COL_MSD_SMALL_N codes, 16384 up to COL_MSD_MAX_N (uniform scenes: n / 256 per bucket +- 4 sigma)
+#define COL_MSD_SMALL_N 1900000u
+#define COL_MSD_MAX_N 4050000u
+// the Morton kernel's tile under the MSD plan that gathers its buckets from sorted tiles (col_radix_sort_msd_gather): 4096
+// codes from COL_GATHER_BIG_FROM codes on (pieces of ~16 pairs instead of ~4: a 128-byte line of a sorted tile then serves
+// two or three buckets instead of eight), 1024 below, where 4096-code tiles would leave CUs idle
+#define COL_GATHER_BIG_FROM (768u << 10)
+#define COL_MSD_GROUP 32u       // tiles per group sum of the fused MSD pass (radix.hip: MSD_GROUP)
+#define COL_MSD_GROUPS 32u      // group sums per digit: the fused pass takes at most COL_MSD_GROUP * COL_MSD_GROUPS tiles
+#define COL_REGION_BOXES 8      // boxes per rank region on the multi-GPU path (multi.hip: k_region)
+
+// ---- internal entry points, one block per defining file (hidden: not part of the public headers) ----
+// DEVICE-SIDE COUNT (round 4, the multi-GPU step): `n_dev` (may be NULL) points at a device word that holds the real number
+// of spheres; `n` is then a host-known upper bound that sizes grids and scratch, and every kernel works on min(n, *n_dev).
+// reduce.hip -- stage 1 of col_reduce(MINMAX, width 4) only: `parts` partial results of [min row, max row] are left in
+// `partials` (at most COL_MINMAX_PARTS of them); also clears nzero words at `zero` (may be NULL)
+extern "C" int col_minmax4_stage1_zero(void *stream, const void *rows, uint64_t n, int coord_bytes, void *partials, uint32_t *parts,
+                                       uint32_t *zero, uint32_t nzero);
+// morton.hip -- col_morton plus two by-products for col_collide: packed (x, y, z, r) rows and a zeroed word
 extern "C" int col_morton_ex(void *stream, const void *coords, const void *radii, const void *range, uint32_t n,
                              uint32_t padded, int coord_bytes, uint32_t *codes, uint32_t *ids, void *packed,
                              uint32_t *zero_word, uint32_t *publish);
-extern "C" int col_lbvh_ex(void *stream, const uint32_t *codes, const uint32_t *ids, const void *coords, const void *radii,
-                           const void *packed, col_node *nodes, void *bounds, void *scratch, uint32_t n, int coord_bytes,
-                           uint32_t *zero8,       // zero8: words the last kernel clears (the traversal's packet counters / chunk header), or NULL
-                           const uint32_t *n_dev,    // device-side count (see col_morton_tile), or NULL
-                           uint32_t *walk_order,     // the traversal's cost / order arrays (WALK ORDER below), or NULL
-                           int order_mode,           // 1: a dense scene -- longest walks first; 0: only deal the long walks of a small launch
-                           uint32_t nzero = 8,       // how many words at zero8 (8: the packet counters; 16: the chunked walk's whole header)
-                           uint32_t *report_word = nullptr,   // col_radix_bucket_report's word: the report rides in k_chunk's launch (one
-                           uint32_t report_n = 0);            // extra workgroup), report_n = length of `codes` with its pads
-extern "C" int col_radix_sort_msd_dev(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out,
-                                      uint64_t n, void *scratch, uint32_t *oversize, const uint32_t *n_real_dev);   // radix.hip
-
-// col_collide's fused front end for inputs sorted with the 1024-pair tile (fewer launches, same bits):
-//  * col_minmax4_stage1: stage 1 of col_reduce(MINMAX, width 4) only; `parts` partial results of
-//    [min row, max row] are left in `partials` (at most COL_MINMAX_PARTS of them);
-//  * col_morton_tile: col_morton_ex that folds those partials itself (no stage-2 launch) and also
-//    writes a histogram for the radix sort (digit = bits hist_shift..hist_shift+7: 0 for the LSD sort's
-//    pass 0, 22 for the MSD sort's bucket digit), `tile` = 1024 or 4096 codes per block (the sort's
-//    tile, col_radix_tile), digit-major hist[d * nblocks + b] like k_hist; with `gsum` (the MSD plan without a scan launch,
-//    col_radix_sort_msd_fused) tile-major hist[b * 256 + d] instead, each count also added into gsum[(b / COL_MSD_GROUP) * 256 + d],
-//    which must be zero on entry (col_minmax4_stage1_zero clears it in the launch before);
-//  * col_radix_sort_ex(have_hist0 = 1): col_radix_sort that finds the pass-0 histogram already at the
-//    start of `scratch`.
-#define COL_MINMAX_PARTS 256
-// col_radix_sort_msd: one workgroup finishes one of 256 top-digit buckets in LDS -- 8192 pairs per bucket for
-// inputs up to COL_MSD_SMALL_N codes, 16384 up to COL_MSD_MAX_N (uniform scenes: n / 256 per bucket +- 4 sigma)
-#define COL_REGION_BOXES 8      /* boxes per rank region on the multi-GPU path (multi.hip: k_region) */
-#define COL_MSD_SMALL_N 1900000u
-#define COL_MSD_MAX_N 4050000u
-extern "C" int col_minmax4_stage1(void *stream, const void *rows, uint64_t n, int coord_bytes, void *partials, uint32_t *parts);
-extern "C" int col_minmax4_stage1_dev(void *stream, const void *rows, const uint32_t *n_dev, uint32_t n_max, int coord_bytes,
-                                      void *partials, uint32_t *parts);
-// DEVICE-SIDE COUNT (round 4, the multi-GPU step): `n_dev` (may be NULL) points at a device word that holds the real number
-// of spheres; `n` is then a host-known upper bound that sizes grids and scratch, and every kernel works on min(n, *n_dev).
+// ... that folds the bounds partials itself (no stage-2 launch) and also writes a histogram for the radix sort (digit = bits
+// hist_shift..hist_shift+7: 0 for the LSD sort's pass 0, 22 for the MSD sort's bucket digit), `tile` = 1024, 4096 or 8192
+// codes per block (the sort's tile, col_radix_tile), digit-major hist[d * nblocks + b] like k_hist; with `gsum` (the MSD plan
+// without a scan launch, col_radix_sort_msd_fused) tile-major hist[b * 256 + d] instead, each count also added into
+// gsum[(b / COL_MSD_GROUP) * 256 + d], which must be zero on entry (col_minmax4_stage1_zero clears it in the launch before).
+// sorted (1024- or 4096-code tiles, with gsum only): the tile leaves SORTED by the digit, see morton.hip
 extern "C" int col_morton_tile(void *stream, const void *coords, const void *radii, const void *partials, uint32_t parts,
                                uint32_t n, uint32_t padded, int coord_bytes, uint32_t *codes, uint32_t *ids, void *packed,
                                uint32_t *zero_word, uint32_t *hist0, uint32_t tile, uint32_t nblocks, int hist_shift,
-                               uint32_t *publish, const uint32_t *n_dev, uint32_t *gsum,
-                               int sorted);     // sorted (1024- or 4096-code tiles, with gsum only): the tile leaves SORTED by the digit, see morton.hip
-// ... and the MSD finish that gathers its buckets from those sorted tiles (radix.hip, k_bucket_sort GATHER): no global pass
-extern "C" int col_radix_sort_msd_gather(void *stream, const uint32_t *tile_keys, uint32_t *keys_out, const uint32_t *tile_vals,
-                                         uint32_t *vals_out, uint32_t n_bound, uint64_t padded, void *scratch, uint32_t *oversize,
-                                         const uint32_t *n_dev, const uint32_t *gsum, uint32_t tile);
-// the tile of that plan: 4096 codes from COL_GATHER_BIG_FROM codes on (pieces of ~16 pairs instead of ~4: a 128-byte line of a
-// sorted tile then serves two or three buckets instead of eight), 1024 below, where 4096-code tiles would leave CUs idle
-#define COL_GATHER_BIG_FROM (768u << 10)
-#define COL_MSD_GROUP 32u       /* tiles per group sum of the fused MSD pass (radix.hip: MSD_GROUP) */
-#define COL_MSD_GROUPS 32u      /* group sums per digit: the fused pass takes at most COL_MSD_GROUP * COL_MSD_GROUPS tiles */
-extern "C" int col_minmax4_stage1_zero(void *stream, const void *rows, uint64_t n, int coord_bytes, void *partials, uint32_t *parts,
-                                       uint32_t *zero, uint32_t nzero);      // col_minmax4_stage1 that also clears nzero words at `zero`
+                               uint32_t *publish, const uint32_t *n_dev, uint32_t *gsum, int sorted);
+// radix.hip -- col_radix_sort; have_hist0 = 1: the pass-0 histogram is already at the start of `scratch`
+extern "C" int col_radix_sort_ex(void *stream, const void *keys, void *keys_out, const void *vals, void *vals_out,
+                                 uint64_t n, int key_bytes, int val_bytes, void *scratch, int copy_back, int have_hist0);
+// (u32 key, u32 value) pairs whose keys are below 2^(8 * passes): only that many digit passes
+extern "C" int col_radix_sort_low_passes(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals,
+                                         uint32_t *vals_out, uint64_t n, void *scratch, int passes);
+// col_radix_sort_msd without the scan launch, on what col_morton_tile(gsum) left; `fused`: col_radix_msd_fused_bytes() bytes
 extern "C" size_t col_radix_msd_fused_bytes(void);
 extern "C" int col_radix_sort_msd_fused(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out,
                                         uint64_t n, void *scratch, uint32_t *oversize, const uint32_t *n_real_dev, uint32_t *fused);
-extern "C" int col_radix_sort_ex(void *stream, const void *keys, void *keys_out, const void *vals, void *vals_out,
-                                 uint64_t n, int key_bytes, int val_bytes, void *scratch, int copy_back, int have_hist0);
-
+// ... and the MSD finish that gathers its buckets from col_morton_tile(sorted)'s tiles (k_bucket_sort GATHER): no global pass
+extern "C" int col_radix_sort_msd_gather(void *stream, const uint32_t *tile_keys, uint32_t *keys_out, const uint32_t *tile_vals,
+                                         uint32_t *vals_out, uint32_t n_bound, uint64_t padded, void *scratch, uint32_t *oversize,
+                                         const uint32_t *n_dev, const uint32_t *gsum, uint32_t tile);
+// the largest top-digit bucket of n sorted codes -> *word (col_bucket_report_block below)
+extern "C" int col_radix_bucket_report(void *stream, const uint32_t *sorted_codes, uint64_t n, uint32_t *word);
+// lbvh.hip -- col_lbvh with `packed` rows (optional, see col_morton_ex) and with what the build does for the walk that
+// follows it.  Host side only: the kernels take these one by one.
+struct col_walk_prep {
+    uint32_t *zero = nullptr;            // words the last kernel clears (the walk's packet counters / chunk header), or NULL
+    uint32_t nzero = 8;                  // how many: 8 (the packet counters) or 16 (the chunked walk's whole header)
+    const uint32_t *n_dev = nullptr;     // device-side count, or NULL
+    uint32_t *walk_order = nullptr;      // the walk's cost / order arrays (WALK ORDER below), or NULL
+    int order_mode = 0;                  // 1: a dense scene -- longest walks first; 0: only deal the long walks of a small launch
+    uint32_t *report_word = nullptr;     // col_radix_bucket_report's word: the report rides in k_chunk's launch (one extra
+    uint32_t report_n = 0;               // workgroup), report_n = length of `codes` with its pads
+};
+extern "C" int col_lbvh_ex(void *stream, const uint32_t *codes, const uint32_t *ids, const void *coords, const void *radii,
+                           const void *packed, col_node *nodes, void *bounds, void *scratch, uint32_t n, int coord_bytes,
+                           const col_walk_prep &w);
+// bvh.hip -- the whole path's walks: col_traverse with the dynamic packet order (`sched`: eight zeroed words, or NULL) and
+// col_traverse_chunked with a header that is already clear (hdr_cleared), both with a device-side count and a walk order
+extern "C" int col_traverse_walk(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const void *bounds,
+                                 uint32_t n, int coord_bytes, uint32_t *sched, const uint32_t *n_dev, uint32_t *walk_order);
+extern "C" int col_traverse_chunked_walk(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const void *bounds,
+                                         uint32_t n, int coord_bytes, void *scratch, const uint32_t *n_dev, uint32_t *walk_order, int hdr_cleared);
+extern "C" int col_traverse_dynamic_order(uint32_t n);      // 1: col_collide's exact walk of n spheres takes the dynamic packet order
+// ghost spheres as packets of 64 Morton-sorted queries (multi.hip: col_traverse_ghost_slots)
 extern "C" int col_traverse_ghost_packets(void *stream, uint32_t *pairs, uint32_t *counter, uint32_t capacity, const void *bounds,
-                                          uint32_t n, int coord_bytes, const uint32_t *rec, const uint32_t *order,
-                                          const uint32_t *count, uint32_t max_ghosts, const uint32_t *local_gids,
-                                          const uint32_t *n_dev);   // bvh.hip (n_dev: device-side count of the local tree, or NULL)
-extern "C" int col_radix_sort_low_passes(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals,
-                                         uint32_t *vals_out, uint64_t n, void *scratch, int passes);      // radix.hip
-extern "C" int col_radix_bucket_report(void *stream, const uint32_t *sorted_codes, uint64_t n, uint32_t *word);   // see radix.hip
+                                          uint32_t n, int coord_bytes, const uint32_t *rec, const uint32_t *order, const uint32_t *count,
+                                          uint32_t max_ghosts, const uint32_t *local_gids, const uint32_t *n_dev);
 
 static inline hipStream_t col_stream(void *s) { return (hipStream_t)s; }
 
 static inline uint64_t col_ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }      // scratch segments start 256-byte aligned
 
 #ifdef __HIPCC__
 typedef unsigned long long u64;

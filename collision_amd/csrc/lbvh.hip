@@ -1315,7 +1315,6 @@ __global__ __launch_bounds__(256) void k_cross(T *__restrict__ bounds, const u32
 constexpr int DBG_WIDE = 1024, DBG_ORDER = 4096, DBG_TABLES = 32768;
 int g_dbg = 0;
 float g_block_k = 3.0f;   // leaf-block density criterion (col_debug_leaf_blocks): node width <= k x leaf width; 0 = no marks
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Layout {
     size_t other_end, partial, cross, tab[3], total;
@@ -1342,8 +1341,8 @@ Layout layout(uint32_t n, int coord_bytes) {
 
 template <typename T>
 int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const T *radii, const T *packed,
-        col_node *nodes, T *bounds, char *scratch, u32 n, u32 *zero8, const u32 *n_dev, u32 *walk_order, int order_mode,
-        u32 nzero, u32 *report_word, u32 report_n) {
+        col_node *nodes, T *bounds, char *scratch, u32 n, const col_walk_prep &w) {
+    u32 *report_word = w.report_word;
     const Layout L = layout(n, sizeof(T));
     u32 *other_end = (u32 *)(scratch + L.other_end);
     T *partial = (T *)(scratch + L.partial);
@@ -1354,37 +1353,37 @@ int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const 
     bool ordered_by_chunk = false;       // the production k_chunk orders the traversal's packets itself; otherwise k_cross does
     if (n < (1u << 30) && !(g_dbg & DBG_WIDE)) {
         // [order_packets workgroups][chunk and search workgroups: PLACES][report workgroup]
-        const dim3 grid((walk_order ? 8u * COL_ORDER_SLICES : 0u) + place_blocks(nchunks) + (report_word ? 1u : 0u));
+        const dim3 grid((w.walk_order ? 8u * COL_ORDER_SLICES : 0u) + place_blocks(nchunks) + (report_word ? 1u : 0u));
         if (nodes)
             k_chunk<T, true><<<grid, dim3(C), 0, s>>>(
-                codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, n_dev, walk_order, order_mode,
-                report_word, report_n);
+                codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, w.n_dev, w.walk_order, w.order_mode,
+                report_word, w.report_n);
         else                            // no Node array asked for: the instance without its stores
             k_chunk<T, false><<<grid, dim3(C), 0, s>>>(
-                codes, ids, coords, radii, packed, nullptr, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, n_dev, walk_order, order_mode,
-                report_word, report_n);
+                codes, ids, coords, radii, packed, nullptr, bounds, other_end, partial, cross, (T *)tabs.t[0], n, (T)g_block_k, w.n_dev, w.walk_order, w.order_mode,
+                report_word, w.report_n);
         ordered_by_chunk = true;
         report_word = nullptr;          // done in that launch
     } else if (nodes)
         k_chunk_wide<T, true><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nodes, bounds, other_end, partial, cross,
-                                                                 (T *)tabs.t[0], n, (T)g_block_k, n_dev);
+                                                                 (T *)tabs.t[0], n, (T)g_block_k, w.n_dev);
     else
         k_chunk_wide<T, false><<<dim3(nchunks), dim3(C), 0, s>>>(codes, ids, coords, radii, packed, nullptr, bounds, other_end, partial, cross,
-                                                                  (T *)tabs.t[0], n, (T)g_block_k, n_dev);
+                                                                  (T *)tabs.t[0], n, (T)g_block_k, w.n_dev);
     COL_LAUNCH_OK();
     if (report_word) {                  // (k_chunk_wide has no report workgroup: the report's own launch)
-        const int rc = col_radix_bucket_report((void *)s, codes, report_n, report_word);
+        const int rc = col_radix_bucket_report((void *)s, codes, w.report_n, report_word);
         if (rc) return rc;
     }
     if (nchunks < 2) {                  // every node lives inside the single chunk: no k_cross, so clear the packet counters here
-        if (zero8) COL_HIP(hipMemsetAsync(zero8, 0, nzero * sizeof(u32), s));
+        if (w.zero) COL_HIP(hipMemsetAsync(w.zero, 0, w.nzero * sizeof(u32), s));
         return COL_OK;
     }
     const unsigned cross_blocks = (unsigned)col_ceil_div((uint64_t)nchunks * CROSS_CAP, 256);
-    const dim3 cross_grid(cross_blocks + (walk_order && !ordered_by_chunk ? 8u * COL_ORDER_SLICES : 0u));
+    const dim3 cross_grid(cross_blocks + (w.walk_order && !ordered_by_chunk ? 8u * COL_ORDER_SLICES : 0u));
     if (nchunks <= CROSS_DIRECT_MAX_CHUNKS && !(g_dbg & DBG_TABLES)) {     // k_cross reads the chunk totals itself: no tables, no k_group
-        k_cross<T, true><<<cross_grid, dim3(256), 0, s>>>(bounds, other_end, partial, cross, tabs, n, nchunks, -1, zero8,
-                                                          n_dev, walk_order, cross_blocks, order_mode, nzero);
+        k_cross<T, true><<<cross_grid, dim3(256), 0, s>>>(bounds, other_end, partial, cross, tabs, n, nchunks, -1, w.zero,
+                                                          w.n_dev, w.walk_order, cross_blocks, w.order_mode, w.nzero);
         COL_LAUNCH_OK();
         return COL_OK;
     }
@@ -1392,12 +1391,12 @@ int run(hipStream_t s, const u32 *codes, const u32 *ids, const T *coords, const 
     for (int h = 0; h < 3; h++) {
         if (h > 0 && L.count[h] <= LIN) { lin = h; break; }      // k_cross scans this level's few entries itself
         const u32 groups = (u32)col_ceil_div(L.count[h], C);
-        k_group<T><<<dim3(groups), dim3(C), 0, s>>>((T *)tabs.t[h], L.count[h], h + 1 < 3 ? (T *)tabs.t[h + 1] : nullptr, n, n_dev, h);
+        k_group<T><<<dim3(groups), dim3(C), 0, s>>>((T *)tabs.t[h], L.count[h], h + 1 < 3 ? (T *)tabs.t[h + 1] : nullptr, n, w.n_dev, h);
         COL_LAUNCH_OK();
         if (groups < 2) break;
     }
-    k_cross<T><<<cross_grid, dim3(256), 0, s>>>(bounds, other_end, partial, cross, tabs, n, nchunks, lin, zero8,
-                                                n_dev, walk_order, cross_blocks, order_mode, nzero);
+    k_cross<T><<<cross_grid, dim3(256), 0, s>>>(bounds, other_end, partial, cross, tabs, n, nchunks, lin, w.zero,
+                                                w.n_dev, w.walk_order, cross_blocks, w.order_mode, w.nzero);
     COL_LAUNCH_OK();
     return COL_OK;
 }
@@ -1418,23 +1417,20 @@ size_t col_lbvh_scratch_bytes(uint32_t n, int coord_bytes) { return layout(n, co
 
 // `packed`: optional (x, y, z, r) rows indexed like coords (see col_morton_ex); coords/radii are then unused.
 int col_lbvh_ex(void *stream, const uint32_t *codes, const uint32_t *ids, const void *coords, const void *radii,
-                const void *packed, col_node *nodes, void *bounds, void *scratch, uint32_t n, int coord_bytes, uint32_t *zero8,
-                const uint32_t *n_dev, uint32_t *walk_order, int order_mode, uint32_t nzero, uint32_t *report_word, uint32_t report_n) {
+                const void *packed, col_node *nodes, void *bounds, void *scratch, uint32_t n, int coord_bytes, const col_walk_prep &w) {
     if (n == 0) return COL_OK;
-    if (n >= 0x80000000u || nzero > 256u) return COL_EINVAL;
+    if (n >= 0x80000000u || w.nzero > 256u) return COL_EINVAL;
     if (!scratch) return COL_ENOSCRATCH;
     if (coord_bytes == 4)
-        return run<float>(col_stream(stream), codes, ids, (const float *)coords, (const float *)radii, (const float *)packed,
-                          nodes, (float *)bounds, (char *)scratch, n, zero8, n_dev, walk_order, order_mode, nzero, report_word, report_n);
+        return run<float>(col_stream(stream), codes, ids, (const float *)coords, (const float *)radii, (const float *)packed, nodes, (float *)bounds, (char *)scratch, n, w);
     if (coord_bytes == 8)
-        return run<double>(col_stream(stream), codes, ids, (const double *)coords, (const double *)radii,
-                           (const double *)packed, nodes, (double *)bounds, (char *)scratch, n, zero8, n_dev, walk_order, order_mode, nzero, report_word, report_n);
+        return run<double>(col_stream(stream), codes, ids, (const double *)coords, (const double *)radii, (const double *)packed, nodes, (double *)bounds, (char *)scratch, n, w);
     return COL_EINVAL;
 }
 
 int col_lbvh(void *stream, const uint32_t *codes, const uint32_t *ids, const void *coords, const void *radii,
              col_node *nodes, void *bounds, void *scratch, uint32_t n, int coord_bytes) {
-    return col_lbvh_ex(stream, codes, ids, coords, radii, nullptr, nodes, bounds, scratch, n, coord_bytes, nullptr, nullptr, nullptr, 0);
+    return col_lbvh_ex(stream, codes, ids, coords, radii, nullptr, nodes, bounds, scratch, n, coord_bytes, col_walk_prep{});
 }
 
 }  // extern "C"

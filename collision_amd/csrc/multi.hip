@@ -964,10 +964,14 @@ int col_pack_slots(void *stream, const void *rows, const uint32_t *gids, const u
     return COL_OK;
 }
 
-size_t col_ghost_scratch_bytes(uint32_t n_slots, uint32_t slot_records) {
-    const uint64_t e = (uint64_t)n_slots * slot_records;
-    return 4 * (((size_t)e * 4 + 255) & ~(size_t)255) + col_radix_scratch_bytes(e, 4, 4) + 256;
+// the packet walk's scratch: keys and values of the ghosts' coarse Morton sort, in and out, then the sort's own scratch
+struct GhostLayout { size_t keys0, vals0, keys1, vals1, sort, total; };
+static GhostLayout ghost_layout(uint32_t n_slots, uint32_t slot_records) {
+    const uint64_t e = (uint64_t)n_slots * slot_records, seg = align256(e * 4);
+    return {0, seg, 2 * seg, 3 * seg, 4 * seg, 4 * seg + col_radix_scratch_bytes(e, 4, 4) + 256};
 }
+
+size_t col_ghost_scratch_bytes(uint32_t n_slots, uint32_t slot_records) { return ghost_layout(n_slots, slot_records).total; }
 
 // scratch: col_ghost_scratch_bytes(n_slots, slot_records) bytes, or NULL for the lane-per-query walk (k_ghost).
 int col_traverse_ghost_slots(void *stream, const void *rec, uint32_t n_slots, uint32_t slot_records, const void *bounds,
@@ -986,10 +990,10 @@ int col_traverse_ghost_slots_dev(void *stream, const void *rec, uint32_t n_slots
     hipStream_t s = col_stream(stream);
     const uint64_t e = (uint64_t)n_slots * slot_records;
     if (scratch && local_gids && e < 0xFFFFFFFFull && (uint64_t)n_slots * (slot_records + 1) < 0xFFFFFFFFull) {
-        const size_t seg = ((size_t)e * 4 + 255) & ~(size_t)255;
+        const GhostLayout L = ghost_layout(n_slots, slot_records);
         char *p = (char *)scratch;
-        u32 *keys0 = (u32 *)p, *vals0 = (u32 *)(p + seg), *keys1 = (u32 *)(p + 2 * seg), *vals1 = (u32 *)(p + 3 * seg);
-        void *sort_scratch = p + 4 * seg;
+        u32 *keys0 = (u32 *)(p + L.keys0), *vals0 = (u32 *)(p + L.vals0), *keys1 = (u32 *)(p + L.keys1), *vals1 = (u32 *)(p + L.vals1);
+        void *sort_scratch = p + L.sort;
         dim3 grid(blocks_for(slot_records), n_slots);
         COL_BY_COORD((k_ghost_codes<float><<<grid, dim3(256), 0, s>>>((const u32 *)rec, slot_records, (const float4 *)bounds, keys0, vals0, flags)),
                      (k_ghost_codes<double><<<grid, dim3(256), 0, s>>>((const u32 *)rec, slot_records, (const double4 *)bounds, keys0, vals0, flags)));

@@ -917,7 +917,6 @@ __global__ __launch_bounds__(COL_WAVE) void k_ref_scatter(const K *keys, K *keys
 // Process-wide diagnostics switch (col_debug_radix_tile): it changes the tile class for EVERY caller in the process and is
 // not synchronised -- set it from one thread, with no sort in flight.
 int g_radix_tile_override = 0;      // 0 = automatic, else 1024 / 4096 / 8192 / 16384
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline bool huge_ok(int key_bytes, int val_bytes) { return key_bytes == 4 && val_bytes == 0; }
 inline u32 tile_auto(uint64_t n, int key_bytes, int val_bytes) {
     u32 t = n < SMALL_N ? (u32)(NT_SMALL * IT_SMALL) : n < BIG_N ? (u32)(NT_MID * IT_BIG) : (u32)(NT_BIG * IT_BIG);
@@ -946,6 +945,28 @@ inline size_t max_tiles_upto(uint64_t n, int key_bytes) {
     if (n >= BIG_N && key_bytes != 8) m = std::max(m, (size_t)col_ceil_div(n, NT_BIG * IT_BIG));
     if (g_radix_tile_override) m = std::max(m, (size_t)col_ceil_div(n, NT_SMALL * IT_SMALL));
     return m;
+}
+
+// The sort's scratch for `nb` tiles of n keys: histogram (at offset 0: col_morton_tile and col_radix_sort_msd's callers write it
+// there) | scan scratch | ping-pong keys | ping-pong values, then 256 spare bytes.  The size query takes nb = max_tiles_upto(n), every
+// sort the nb of its own call: the first two segments grow with nb, so a carve never ends beyond the size reported for its n.
+struct RadixLayout { size_t hist, scan, keys, vals, total; };
+inline RadixLayout radix_layout(uint64_t n, int key_bytes, int val_bytes, size_t nb) {
+    RadixLayout L;
+    size_t off = 0;
+    L.hist = off; off += align256((size_t)RDIG * nb * sizeof(u32));
+    L.scan = off; off += align256(col_scan_scratch_bytes((uint64_t)RDIG * nb));
+    L.keys = off; off += align256((size_t)n * key_bytes);
+    L.vals = off; off += align256((size_t)n * val_bytes);
+    L.total = off + 256;
+    return L;
+}
+// Two u32 arrays of n behind the whole scratch of the (key_bytes, val_bytes) sort: the widened keys of a narrow-key sort or
+// the index ramp of a wide-value sort, and the sorted image of either.
+struct TailLayout { size_t in, out, total; };
+inline TailLayout tail_layout(uint64_t n, int key_bytes, int val_bytes) {
+    const size_t base = col_radix_scratch_bytes(n, key_bytes, val_bytes), seg = align256((size_t)n * 4);
+    return {base, base + seg, base + 2 * seg};
 }
 
 inline u32 hist_group(u32 nblocks) {
@@ -1142,14 +1163,9 @@ uint32_t col_radix_tile(uint64_t n, int key_bytes, int val_bytes) {
 // Monotone in n: sized for the largest histogram any n' <= n can need (see max_tiles_upto), so a scratch
 // buffer sized for n serves every smaller sort / col_collide call as well.
 size_t col_radix_scratch_bytes(uint64_t n, int key_bytes, int val_bytes) {
-    if (narrow_key(key_bytes))       // the u32 sort + the widened keys and their sorted image
-        return col_radix_scratch_bytes(n, 4, val_bytes) + 2 * align256((size_t)n * 4);
-    if (wide_value(val_bytes))       // (key, index) sort + the index ramp and its sorted image
-        return col_radix_scratch_bytes(n, key_bytes, 4) + 2 * align256((size_t)n * 4);
-    const size_t nb = max_tiles_upto(n, key_bytes);
-    const size_t hist = align256((size_t)RDIG * nb * sizeof(u32));
-    return hist + align256(col_scan_scratch_bytes((uint64_t)RDIG * nb)) + align256((size_t)n * key_bytes) +
-           align256((size_t)n * val_bytes) + 256;
+    if (narrow_key(key_bytes)) return tail_layout(n, 4, val_bytes).total;       // the u32 sort + the widened keys
+    if (wide_value(val_bytes)) return tail_layout(n, key_bytes, 4).total;       // (key, index) sort + the index ramp
+    return radix_layout(n, key_bytes, val_bytes, max_tiles_upto(n, key_bytes)).total;
 }
 
 int col_radix_tile_override_active(void) { return g_radix_tile_override != 0; }
@@ -1182,6 +1198,16 @@ __global__ __launch_bounds__(RDIG) void k_bucket_report(const u32 *__restrict__ 
     col_bucket_report_block(sorted, n, word, s_start);
 }
 
+// The MSD plan's LDS finish of the buckets that `offsets` locates (k_bucket_sort).  A uniform scene puts n / 256 codes into a
+// bucket: the 8192-pair finish up to ~1.9 M codes, the 16384-pair one above.
+static int msd_finish(hipStream_t s, u32 *tmp_keys, u32 *tmp_vals, u32 *keys_out, u32 *vals_out, uint64_t n, const u32 *offsets,
+                      u32 nblocks, u32 *oversize, const u32 *n_real_dev) {
+    if (n <= COL_MSD_SMALL_N) k_bucket_sort<8><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, offsets, nblocks, oversize, n_real_dev);
+    else k_bucket_sort<16><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, offsets, nblocks, oversize, n_real_dev);
+    COL_LAUNCH_OK();
+    return COL_OK;
+}
+
 // MSD sort of (u32 key, u32 value) pairs whose keys are 30-bit codes (or 0xFFFFFFFF pads), for inputs up to
 // COL_MSD_MAX_N pairs.  The histogram of the bucket digit (bits 22..29, digit-major, one row entry per tile
 // of col_radix_tile(n) pairs) must already be at the start of `scratch` (col_morton_tile writes it).
@@ -1189,40 +1215,27 @@ __global__ __launch_bounds__(RDIG) void k_bucket_report(const u32 *__restrict__ 
 // that did not fit LDS, if any.
 int col_radix_sort_msd(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out,
                        uint64_t n, void *scratch, uint32_t *oversize) {
-    return col_radix_sort_msd_dev(stream, keys, keys_out, vals, vals_out, n, scratch, oversize, nullptr);
-}
-
-// ... with the number of real codes on the device (pads beyond it: see k_bucket_sort); internal (col_common.h)
-int col_radix_sort_msd_dev(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out,
-                           uint64_t n, void *scratch, uint32_t *oversize, const uint32_t *n_real_dev) {
     if (n == 0) return COL_OK;
     if (!scratch || !vals || !vals_out) return COL_EINVAL;
     if (n > COL_MSD_MAX_N) return COL_EINVAL;
     const u32 tile = tile_auto(n, 4, 4);                  // (a forced tile class does not apply here)
     hipStream_t s = col_stream(stream);
     const size_t nb = col_ceil_div(n, tile);
-    char *p = (char *)scratch;
-    u32 *hist = (u32 *)p;              p += align256((size_t)RDIG * nb * sizeof(u32));
-    void *scan_scratch = p;            p += align256(col_scan_scratch_bytes((uint64_t)RDIG * nb));
-    u32 *tmp_keys = (u32 *)p;          p += align256((size_t)n * 4);
-    u32 *tmp_vals = (u32 *)p;
-    int rc = col_scan_u32(stream, hist, (uint64_t)RDIG * nb, scan_scratch);
+    const RadixLayout L = radix_layout(n, 4, 4, nb);
+    u32 *hist = (u32 *)((char *)scratch + L.hist);
+    u32 *tmp_keys = (u32 *)((char *)scratch + L.keys), *tmp_vals = (u32 *)((char *)scratch + L.vals);
+    int rc = col_scan_u32(stream, hist, (uint64_t)RDIG * nb, (char *)scratch + L.scan);
     if (rc) return rc;
     if (tile == (u32)(NT_SMALL * IT_SMALL)) rc = launch_scatter_it<u32, IT_SMALL, NT_SMALL>(s, keys, tmp_keys, vals, tmp_vals, n, 4, BS_SHIFT, hist);
     else rc = launch_scatter_it<u32, IT_BIG, NT_MID>(s, keys, tmp_keys, vals, tmp_vals, n, 4, BS_SHIFT, hist);
     if (rc) return rc;
-    // a uniform scene puts n / 256 codes into a bucket: the 8192-pair finish up to ~1.9 M, the 16384-pair one above
-    if (n <= COL_MSD_SMALL_N)
-        k_bucket_sort<8><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, hist, (u32)nb, oversize, n_real_dev);
-    else
-        k_bucket_sort<16><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, hist, (u32)nb, oversize, n_real_dev);
-    COL_LAUNCH_OK();
-    return COL_OK;
+    return msd_finish(s, tmp_keys, tmp_vals, keys_out, vals_out, n, hist, (u32)nb, oversize, nullptr);
 }
 
-// col_radix_sort_msd_dev for col_collide without the scan launch (k_scatter, FUSED): the start of `scratch` holds the unscanned
+// col_radix_sort_msd for col_collide without the scan launch (k_scatter, FUSED): the start of `scratch` holds the unscanned
 // counts TILE-MAJOR, `fused` (col_radix_msd_fused_bytes()) the group sums -- col_morton_tile(gsum) writes both, into group sums
-// that were zero -- followed by the 256 bucket starts the pass leaves for k_bucket_sort.  Internal (col_common.h).
+// that were zero -- followed by the 256 bucket starts the pass leaves for k_bucket_sort; n_real_dev: the number of real codes
+// on the device, or NULL (pads beyond it: see k_bucket_sort).  Internal (col_common.h).
 size_t col_radix_msd_fused_bytes(void) { return (size_t)(MSD_GROUPS + 1) * RDIG * sizeof(u32); }
 int col_radix_sort_msd_fused(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals, uint32_t *vals_out,
                              uint64_t n, void *scratch, uint32_t *oversize, const uint32_t *n_real_dev, uint32_t *fused) {
@@ -1233,11 +1246,9 @@ int col_radix_sort_msd_fused(void *stream, const uint32_t *keys, uint32_t *keys_
     hipStream_t s = col_stream(stream);
     const size_t nb = col_ceil_div(n, tile);
     if (nb > (size_t)MSD_GROUP * MSD_GROUPS) return COL_EINVAL;
-    char *p = (char *)scratch;
-    const u32 *counts = (const u32 *)p; p += align256((size_t)RDIG * nb * sizeof(u32));
-    p += align256(col_scan_scratch_bytes((uint64_t)RDIG * nb));
-    u32 *tmp_keys = (u32 *)p;          p += align256((size_t)n * 4);
-    u32 *tmp_vals = (u32 *)p;
+    const RadixLayout L = radix_layout(n, 4, 4, nb);
+    const u32 *counts = (const u32 *)((char *)scratch + L.hist);
+    u32 *tmp_keys = (u32 *)((char *)scratch + L.keys), *tmp_vals = (u32 *)((char *)scratch + L.vals);
     u32 *starts = fused + MSD_GROUPS * RDIG;
     const FusedOn f{fused, starts};
     if (tile == (u32)(NT_SMALL * IT_SMALL))
@@ -1246,12 +1257,7 @@ int col_radix_sort_msd_fused(void *stream, const uint32_t *keys, uint32_t *keys_
         k_scatter<u32, 4, IT_BIG, NT_MID, true><<<dim3((unsigned)nb), dim3(NT_MID), 0, s>>>(keys, tmp_keys, vals, tmp_vals, n, (u32)nb, BS_SHIFT, counts, f);
     COL_LAUNCH_OK();
     // (one entry per bucket: k_bucket_sort reads offsets[d * nblocks] with nblocks = 1)
-    if (n <= COL_MSD_SMALL_N)
-        k_bucket_sort<8><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, starts, 1u, oversize, n_real_dev);
-    else
-        k_bucket_sort<16><<<dim3(RDIG), dim3(BS_NT), 0, s>>>(tmp_keys, tmp_vals, keys_out, vals_out, (u32)n, starts, 1u, oversize, n_real_dev);
-    COL_LAUNCH_OK();
-    return COL_OK;
+    return msd_finish(s, tmp_keys, tmp_vals, keys_out, vals_out, n, starts, 1u, oversize, n_real_dev);
 }
 
 // The MSD plan of col_collide without ANY global pass, for the 1024-pair tile class (k_bucket_sort, GATHER): tile_keys / tile_vals
@@ -1268,11 +1274,9 @@ int col_radix_sort_msd_gather(void *stream, const uint32_t *tile_keys, uint32_t 
     if (nb > (size_t)MSD_GROUP * MSD_GROUPS || nb > (size_t)BS_NT) return COL_EINVAL;
     u32 glog = 0;
     while (glog < GATHER_GLOG_MAX && (nb << (glog + 1)) <= (size_t)BS_NT) glog++;
-    char *p = (char *)scratch;
-    const u32 *table = (const u32 *)p; p += align256((size_t)RDIG * nb * sizeof(u32));
-    p += align256(col_scan_scratch_bytes((uint64_t)RDIG * nb));
-    u32 *x_keys = (u32 *)p;            p += align256((size_t)padded * 4);
-    u32 *x_vals = (u32 *)p;
+    const RadixLayout L = radix_layout(padded, 4, 4, nb);       // (nb tiles of the Morton kernel's `tile`: never more than the sort's own)
+    const u32 *table = (const u32 *)((char *)scratch + L.hist);
+    u32 *x_keys = (u32 *)((char *)scratch + L.keys), *x_vals = (u32 *)((char *)scratch + L.vals);
     const GatherOn ga{gsum, n_bound, tile, glog, x_keys, x_vals};
     k_bucket_sort<8, true><<<dim3(RDIG), dim3(BS_NT), 0, col_stream(stream)>>>((u32 *)tile_keys, (u32 *)tile_vals, keys_out, vals_out, (u32)padded,
                                                                                 table, (u32)nb, oversize, n_dev, ga);
@@ -1280,8 +1284,57 @@ int col_radix_sort_msd_gather(void *stream, const uint32_t *tile_keys, uint32_t 
     return COL_OK;
 }
 
+// radix.py:158-169 leaves a sorted copy in the input buffers too (copy_back)
+static int copy_to_inputs(hipStream_t s, const void *keys, const void *keys_out, const void *vals, const void *vals_out, uint64_t n,
+                          int key_bytes, int val_bytes) {
+    COL_HIP(hipMemcpyAsync((void *)keys, keys_out, (size_t)n * key_bytes, hipMemcpyDeviceToDevice, s));
+    if (val_bytes) COL_HIP(hipMemcpyAsync((void *)vals, vals_out, (size_t)n * val_bytes, hipMemcpyDeviceToDevice, s));
+    return COL_OK;
+}
+
+// `passes` 8-bit digit passes from the least significant byte (= key_bytes for a full sort; fewer when the upper
+// key bytes are known to be zero); the last pass lands in *_out.
 static int sort_passes(void *stream, const void *keys, void *keys_out, const void *vals, void *vals_out,
-                       uint64_t n, int key_bytes, int val_bytes, void *scratch, int copy_back, int have_hist0, int passes);
+                       uint64_t n, int key_bytes, int val_bytes, void *scratch, int copy_back, int have_hist0, int passes) {
+    if (wide_value(val_bytes)) {
+        // values of a width the scatter kernel does not move: sort (key, index), gather the values once
+        if (n >= 0xFFFFFFFFull || (key_bytes != 4 && key_bytes != 8)) return COL_EINVAL;
+        if (n == 0) return COL_OK;
+        if (!scratch) return COL_ENOSCRATCH;
+        hipStream_t s = col_stream(stream);
+        const TailLayout X = tail_layout(n, key_bytes, 4);
+        u32 *iota = (u32 *)((char *)scratch + X.in), *sorted_idx = (u32 *)((char *)scratch + X.out);
+        k_iota<<<dim3((unsigned)col_ceil_div(n, 256)), dim3(256), 0, s>>>(iota, n);
+        COL_LAUNCH_OK();
+        int rc = sort_passes(stream, keys, keys_out, iota, sorted_idx, n, key_bytes, 4, scratch, 0, 0, passes);
+        if (rc) return rc;
+        if ((rc = gather_values(s, vals, sorted_idx, vals_out, n, val_bytes))) return rc;
+        return copy_back ? copy_to_inputs(s, keys, keys_out, vals, vals_out, n, key_bytes, val_bytes) : COL_OK;
+    }
+    if (bad_sizes(n, key_bytes, val_bytes)) return COL_EINVAL;
+    if (n == 0) return COL_OK;
+    if (!scratch) return COL_ENOSCRATCH;
+    hipStream_t s = col_stream(stream);
+    const size_t nb = tiles_of(n, key_bytes, val_bytes);
+    const RadixLayout L = radix_layout(n, key_bytes, val_bytes, nb);       // (carved for THIS n: never more than col_radix_scratch_bytes(n))
+    u32 *hist = (u32 *)((char *)scratch + L.hist);
+    void *scan_scratch = (char *)scratch + L.scan, *tmp_keys = (char *)scratch + L.keys, *tmp_vals = (char *)scratch + L.vals;
+    const void *src_k = keys, *src_v = vals;       // 8-bit digits; the destinations alternate so that the last pass lands in *_out
+    for (int pass = 0; pass < passes; pass++) {
+        void *dst_k = ((passes - 1 - pass) & 1) ? tmp_keys : keys_out;
+        void *dst_v = ((passes - 1 - pass) & 1) ? tmp_vals : vals_out;
+        int rc = (pass == 0 && have_hist0) ? COL_OK : col_radix_histogram(stream, src_k, n, key_bytes, val_bytes, pass, hist);
+        if (rc) return rc;
+        rc = col_scan_u32(stream, hist, (uint64_t)RDIG * nb, scan_scratch);
+        if (rc) return rc;
+        rc = col_radix_scatter(stream, src_k, dst_k, src_v, dst_v, n, key_bytes, val_bytes, pass, hist);
+        if (rc) return rc;
+        src_k = dst_k;
+        src_v = dst_v;
+    }
+    return copy_back ? copy_to_inputs(s, keys, keys_out, vals, vals_out, n, key_bytes, val_bytes) : COL_OK;
+}
+
 // (u32 key, u32 value) pairs whose keys are below 2^(8 * passes): only that many digit passes (internal)
 int col_radix_sort_low_passes(void *stream, const uint32_t *keys, uint32_t *keys_out, const uint32_t *vals,
                               uint32_t *vals_out, uint64_t n, void *scratch, int passes) {
@@ -1301,9 +1354,6 @@ int col_radix_sort(void *stream, const void *keys, void *keys_out, const void *v
     return col_radix_sort_ex(stream, keys, keys_out, vals, vals_out, n, key_bytes, val_bytes, scratch, copy_back, 0);
 }
 
-static int sort_passes(void *stream, const void *keys, void *keys_out, const void *vals, void *vals_out,
-                       uint64_t n, int key_bytes, int val_bytes, void *scratch, int copy_back, int have_hist0, int passes);
-
 int col_radix_sort_ex(void *stream, const void *keys, void *keys_out, const void *vals, void *vals_out,
                       uint64_t n, int key_bytes, int val_bytes, void *scratch, int copy_back, int have_hist0) {
     if (!vals || !vals_out) val_bytes = 0;
@@ -1313,84 +1363,21 @@ int col_radix_sort_ex(void *stream, const void *keys, void *keys_out, const void
         if (n == 0) return COL_OK;
         if (!scratch) return COL_ENOSCRATCH;
         hipStream_t s = col_stream(stream);
-        char *q = (char *)scratch + col_radix_scratch_bytes(n, 4, val_bytes);
-        u32 *wide_in = (u32 *)q, *wide_out = (u32 *)(q + align256((size_t)n * 4));
+        const TailLayout W = tail_layout(n, 4, val_bytes);
+        u32 *wide_in = (u32 *)((char *)scratch + W.in), *wide_out = (u32 *)((char *)scratch + W.out);
         dim3 grid((unsigned)col_ceil_div(n, 256)), block(256);
         if (key_bytes == 1) k_widen<uint8_t><<<grid, block, 0, s>>>((const uint8_t *)keys, wide_in, n);
         else k_widen<uint16_t><<<grid, block, 0, s>>>((const uint16_t *)keys, wide_in, n);
         COL_LAUNCH_OK();
-        int rc;
-        if (wide_value(val_bytes)) {
-            char *q2 = (char *)scratch + col_radix_scratch_bytes(n, 4, 4);
-            u32 *iota = (u32 *)q2, *sorted_idx = (u32 *)(q2 + align256((size_t)n * 4));
-            k_iota<<<grid, block, 0, s>>>(iota, n);
-            COL_LAUNCH_OK();
-            if ((rc = sort_passes(stream, wide_in, wide_out, iota, sorted_idx, n, 4, 4, scratch, 0, 0, key_bytes))) return rc;
-            if ((rc = gather_values(s, vals, sorted_idx, vals_out, n, val_bytes))) return rc;
-        } else if ((rc = sort_passes(stream, wide_in, wide_out, vals, vals_out, n, 4, val_bytes, scratch, 0, 0, key_bytes))) return rc;
+        // (wide values: sort_passes sorts (key, index) pairs and gathers, its ramp in front of the widened keys)
+        const int rc = sort_passes(stream, wide_in, wide_out, vals, vals_out, n, 4, val_bytes, scratch, 0, 0, key_bytes);
+        if (rc) return rc;
         if (key_bytes == 1) k_narrow<uint8_t><<<grid, block, 0, s>>>(wide_out, (uint8_t *)keys_out, n);
         else k_narrow<uint16_t><<<grid, block, 0, s>>>(wide_out, (uint16_t *)keys_out, n);
         COL_LAUNCH_OK();
-        if (copy_back) {
-            COL_HIP(hipMemcpyAsync((void *)keys, keys_out, (size_t)n * key_bytes, hipMemcpyDeviceToDevice, s));
-            if (val_bytes) COL_HIP(hipMemcpyAsync((void *)vals, vals_out, (size_t)n * val_bytes, hipMemcpyDeviceToDevice, s));
-        }
-        return COL_OK;
+        return copy_back ? copy_to_inputs(s, keys, keys_out, vals, vals_out, n, key_bytes, val_bytes) : COL_OK;
     }
     return sort_passes(stream, keys, keys_out, vals, vals_out, n, key_bytes, val_bytes, scratch, copy_back, have_hist0, key_bytes);
-}
-
-// `passes` 8-bit digit passes from the least significant byte (= key_bytes for a full sort; fewer when the upper
-// key bytes are known to be zero); the last pass lands in *_out.
-static int sort_passes(void *stream, const void *keys, void *keys_out, const void *vals, void *vals_out,
-                       uint64_t n, int key_bytes, int val_bytes, void *scratch, int copy_back, int have_hist0, int passes) {
-    if (wide_value(val_bytes)) {
-        // values of a width the scatter kernel does not move: sort (key, index), gather the values once
-        if (n >= 0xFFFFFFFFull || (key_bytes != 4 && key_bytes != 8)) return COL_EINVAL;
-        if (n == 0) return COL_OK;
-        if (!scratch) return COL_ENOSCRATCH;
-        hipStream_t s = col_stream(stream);
-        char *q = (char *)scratch + col_radix_scratch_bytes(n, key_bytes, 4);
-        u32 *iota = (u32 *)q, *sorted_idx = (u32 *)(q + align256((size_t)n * 4));
-        k_iota<<<dim3((unsigned)col_ceil_div(n, 256)), dim3(256), 0, s>>>(iota, n);
-        COL_LAUNCH_OK();
-        int rc = sort_passes(stream, keys, keys_out, iota, sorted_idx, n, key_bytes, 4, scratch, 0, 0, passes);
-        if (rc) return rc;
-        if ((rc = gather_values(s, vals, sorted_idx, vals_out, n, val_bytes))) return rc;
-        if (copy_back) {
-            COL_HIP(hipMemcpyAsync((void *)keys, keys_out, (size_t)n * key_bytes, hipMemcpyDeviceToDevice, s));
-            COL_HIP(hipMemcpyAsync((void *)vals, vals_out, (size_t)n * val_bytes, hipMemcpyDeviceToDevice, s));
-        }
-        return COL_OK;
-    }
-    if (bad_sizes(n, key_bytes, val_bytes)) return COL_EINVAL;
-    if (n == 0) return COL_OK;
-    if (!scratch) return COL_ENOSCRATCH;
-    hipStream_t s = col_stream(stream);
-    const size_t nb = tiles_of(n, key_bytes, val_bytes);
-    char *p = (char *)scratch;
-    u32 *hist = (u32 *)p;              p += align256((size_t)RDIG * nb * sizeof(u32));
-    void *scan_scratch = p;            p += align256(col_scan_scratch_bytes((uint64_t)RDIG * nb));
-    void *tmp_keys = p;                p += align256((size_t)n * key_bytes);
-    void *tmp_vals = p;                // (carved for THIS n: never more than col_radix_scratch_bytes(n) in total)
-    const void *src_k = keys, *src_v = vals;       // 8-bit digits; the destinations alternate so that the last pass lands in *_out
-    for (int pass = 0; pass < passes; pass++) {
-        void *dst_k = ((passes - 1 - pass) & 1) ? tmp_keys : keys_out;
-        void *dst_v = ((passes - 1 - pass) & 1) ? tmp_vals : vals_out;
-        int rc = (pass == 0 && have_hist0) ? COL_OK : col_radix_histogram(stream, src_k, n, key_bytes, val_bytes, pass, hist);
-        if (rc) return rc;
-        rc = col_scan_u32(stream, hist, (uint64_t)RDIG * nb, scan_scratch);
-        if (rc) return rc;
-        rc = col_radix_scatter(stream, src_k, dst_k, src_v, dst_v, n, key_bytes, val_bytes, pass, hist);
-        if (rc) return rc;
-        src_k = dst_k;
-        src_v = dst_v;
-    }
-    if (copy_back) {   // radix.py:158-169 leaves a sorted copy in the input buffers too
-        COL_HIP(hipMemcpyAsync((void *)keys, keys_out, (size_t)n * key_bytes, hipMemcpyDeviceToDevice, s));
-        if (val_bytes) COL_HIP(hipMemcpyAsync((void *)vals, vals_out, (size_t)n * val_bytes, hipMemcpyDeviceToDevice, s));
-    }
-    return COL_OK;
 }
 
 int col_ref_block_sort(void *stream, void *keys, void *vals, uint64_t n, int key_bytes, int val_bytes,

@@ -298,10 +298,6 @@ int list_by_width(void *stream, const void *values, uint64_t n, int width, const
 
 extern "C" {
 
-int col_minmax4_stage1(void *stream, const void *rows, uint64_t n, int coord_bytes, void *partials, uint32_t *parts) {
-    return col_minmax4_stage1_zero(stream, rows, n, coord_bytes, partials, parts, nullptr, 0);
-}
-
 int col_minmax4_stage1_zero(void *stream, const void *rows, uint64_t n, int coord_bytes, void *partials, uint32_t *parts,
                             uint32_t *zero, uint32_t nzero) {
     if (!zero) nzero = 0;
@@ -323,7 +319,7 @@ int col_minmax4_stage1_zero(void *stream, const void *rows, uint64_t n, int coor
 
 // The same partials with the row count in device memory (*n_dev, at most n_max): the grid is sized for n_max, blocks
 // without rows leave the identity, and min / max being exact and order-independent the fold gives the bits of
-// col_minmax4_stage1 on the true count.
+// col_minmax4_stage1_zero on the true count.
 int col_minmax4_stage1_dev(void *stream, const void *rows, const uint32_t *n_dev, uint32_t n_max, int coord_bytes, void *partials,
                            uint32_t *parts) {
     if (!n_dev || !partials || !parts) return COL_EINVAL;

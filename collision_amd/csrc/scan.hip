@@ -161,7 +161,6 @@ __global__ __launch_bounds__(256) void k_ref_block_scan(u32 *data, uint64_t n, u
     if (i < n) data[i] += block_sums[i / block];
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int scan_rec(hipStream_t s, u32 *data, uint64_t n, char *scratch) {
     if (n == 0) return COL_OK;

@@ -232,7 +232,7 @@ int col_lbvh(void *stream, const uint32_t *codes, const uint32_t *ids, const voi
  * last -- the bucket finish gathers from these tiles, there is no global scatter pass.  ids[0] is then NOT
  * range(padded);
  * bounds (2n-1)*8 scalars; flags 2n-1 uint32; scratch from
- * col_collide_scratch_bytes. */
+ * col_collide_scratch_bytes.  `scratch` is expected 256-byte aligned (what col_malloc, hipMalloc and torch give). */
 size_t col_collide_scratch_bytes(uint32_t n, uint32_t padded, int coord_bytes);
 int col_collide(void *stream, const void *coords, const void *radii, uint32_t n, uint32_t padded,
                 int coord_bytes, uint32_t *codes0, uint32_t *codes1, uint32_t *ids0, uint32_t *ids1,

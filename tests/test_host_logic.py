@@ -262,6 +262,36 @@ def test_scratch_sizes_are_monotone_in_n():
     assert call.col_collide_scratch_bytes(8388096, 8388096, 4) <= call.col_collide_scratch_bytes(8389120, 8389120, 4)
 
 
+# every tile-class boundary of the sort (2^20, 2^23, 2^25), the MSD plan's limits, the gather tile's threshold, and a stride
+SCRATCH_SWEEP = sorted({1, 2, 63, 64, 255, 256, 257, 1000, 1024, 1025, 4096, 5000, 65535, 65536, 262144, 262145, 786431, 786432,
+                        786433, 2 ** 20, 2 ** 20 + 1, 1899999, 1900000, 1900001, 4049999, 4050000, 4050001, 2 ** 23,
+                        2 ** 25 - 1, 2 ** 25, 2 ** 25 + 1, 2 ** 26} | set(range(1, 3000000, 37717)))
+
+
+def test_scratch_sizes_are_monotone_over_the_whole_sweep():
+    """The size queries are the `total` of the layouts the carves read (collide_layout, radix_layout): non-decreasing in n
+    across every boundary at which a tile or a plan changes."""
+    call = _lib.call
+    for cb in (4, 8):
+        sizes = [call.col_collide_scratch_bytes(n, roundUp(n, 128), cb) for n in SCRATCH_SWEEP]
+        assert sizes == sorted(sizes), cb
+    for kb, vb in ((4, 4), (4, 0), (8, 8), (4, 16), (8, 32), (1, 4), (2, 64), (4, 128)):
+        sizes = [call.col_radix_scratch_bytes(n, kb, vb) for n in SCRATCH_SWEEP]
+        assert sizes == sorted(sizes), (kb, vb)
+
+
+def test_collide_scratch_did_not_grow_with_the_layout():
+    """col_collide_scratch_bytes used to be a sum of parts plus 1280 bytes of slack, beside a carve that rounded up five
+    times; it is now the end of that carve.  Against the sizes of the last build with the sum: at most 1024 bytes more -- a
+    255-byte allowance for the base, at most 255 bytes of rounding for each of seven segments, less the 1280 that went."""
+    call = _lib.call
+    for n, padded, cb, before in ((1000, 1024, 4, 397632), (5000, 5120, 4, 645176), (5000, 5120, 8, 1171896),
+                                  (2 ** 20, 2 ** 20, 4, 66060616), (4000000, 4000000, 8, 445166440)):
+        now = call.col_collide_scratch_bytes(n, padded, cb)
+        assert now <= before + 1024, (n, padded, cb, now, before)
+        assert now > call.col_radix_scratch_bytes(padded, 4, 4) + call.col_lbvh_scratch_bytes(n, cb)
+
+
 def test_rendered_reductions_compile_without_a_device():
     """Any accumulator list (reduce.py:9-22) that is not compiled in is rendered into HIP and compiled by hiprtc at run
     time; the rendering and the compile step need no GPU (col_reduce_rtc_check).  Also: what the compiler says about

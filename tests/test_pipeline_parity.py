@@ -29,11 +29,13 @@ def clustered_scene(n, sigma, r, dtype, seed=4):
 
 
 def check_against_oracle(oracle, hip_env, coords, radii, group_size=64, ngroups=8, capacity=None, sort_plan=None,
-                         traverse_plan=None, extra_capacity=0):
+                         traverse_plan=None, extra_capacity=0, prepare=None):
     ctx, cq = hip_env
     dt = coords.dtype
     n = len(coords)
     collider = Collider(ctx, n, ngroups, group_size, dt)
+    if prepare is not None:            # (the caller's own buffers, tests/test_scratch_guards.py)
+        prepare(collider)
     if sort_plan is not None:
         collider.sort_plan = sort_plan
     if traverse_plan is not None:
