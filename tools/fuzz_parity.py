@@ -1,7 +1,8 @@
 """Randomised parity soak on the GPU box: random scenes (size, distribution, radii, dtype, group size)
 through the whole path against the CPU oracle, every array bit for bit; random radix sorts (size, key
-and value widths, key distributions) against NumPy's stable argsort.  Test infrastructure: uses the
-oracle as the checker, like tests/.
+and value widths, key distributions) against NumPy's stable argsort.  Scene kinds 5 and up are the families of the suite's
+scene zoo (tests/zoo.py) with a random seed: the soak and the suite draw from one definition.  Test
+infrastructure: uses the oracle as the checker, like tests/.
 
     python tools/fuzz_parity.py [seconds] [seed] [logfile] [first]     (first: skip the iterations before it)
 COLLISION_FUZZ_TRAVERSE=<col_debug_traverse variant>, e.g. 32768: the dynamic packet order at every size.
@@ -18,6 +19,9 @@ import oracle as oracle_mod                                   # noqa: E402
 from collision_amd import hip                                 # noqa: E402
 from collision_amd._lib import call                           # noqa: E402
 from tests.test_pipeline_parity import check_against_oracle   # noqa: E402
+from tests.zoo import FAMILIES as ZOO, scene as zoo_scene     # noqa: E402
+
+ZOO_MAX_N = {"range_overflow": 20000}                         # (equal codes: a tree by index, every walk visits most of it)
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -48,8 +52,11 @@ while time.time() < t_end:
     n = (int(2 + rng.randint(0, 10) ** 5 * 2 + rng.randint(0, 3000)) if u < 0.65 else int(rng.randint(2, 300000)) if u < 0.9
          else int(rng.randint(1000000, 4300000)))
     dtype = "float32" if rng.rand() < 0.7 else "float64"
-    kind = rng.randint(0, 5)
-    if kind == 0:
+    kind = rng.randint(0, 5 + len(ZOO))
+    if kind >= 5:                                              # a family of the suite's scene zoo (tests/zoo.py), any seed
+        n = min(n, ZOO_MAX_N.get(ZOO[kind - 5], 300000))
+        pts, zoo_radii = zoo_scene(ZOO[kind - 5], n, dtype, seed=int(rng.randint(0, 2 ** 31 - 1)))
+    elif kind == 0:
         pts = rng.random_sample((n, 3))
     elif kind == 1:
         k = rng.randint(1, 9)
@@ -66,13 +73,15 @@ while time.time() < t_end:
     else:                                                      # large offsets, negative coordinates
         pts = rng.random_sample((n, 3)) * 10.0 ** rng.uniform(-2, 3) - 10.0 ** rng.uniform(-2, 3)
     coords = pts.astype(dtype)
-    scale = (coords.max() - coords.min() + 1e-9) * max(n, 2) ** (-1.0 / 3.0)
+    scale = 1.0 if kind >= 5 else (coords.max() - coords.min() + 1e-9) * max(n, 2) ** (-1.0 / 3.0)
     if kind in (1, 2, 3) and n > 20000:                        # dense scenes: keep the pair count checkable
         scale *= 0.05 if n < 1000000 else 0.01
     rk = rng.randint(0, 3)
     radii = (np.full(n, scale * rng.uniform(0.05, 0.6)) if rk == 0 else
              rng.uniform(0.0, scale * 0.8, size=n) if rk == 1 else
              scale * 10.0 ** rng.uniform(-3, -0.1, size=n)).astype(dtype)
+    if kind >= 5:                                              # (the family's own radius law; the draws above keep the stream)
+        radii = zoo_radii
     gs = int(2 ** rng.randint(3, 9))
     scenes += 1
     if scenes >= first:
