@@ -87,7 +87,7 @@ class OracleEngine(_protocol_ops()):
 
     def unpack5(self, rec5, n, rows, gids, radii=None):
         t = self.torch
-        rows[:n] = rec5[:n, :4 * self._wf].contiguous().view(self._f)
+        rows[:n] = rec5[:n, :4 * self._wf].clone(memory_format=t.contiguous_format).view(self._f)   # (0 or 1 rows: .contiguous() copies nothing)
         gids[:n] = rec5[:n, 4 * self._wf]
 
     def collide(self, rows, gids, n):
@@ -136,7 +136,7 @@ class OracleEngine(_protocol_ops()):
             if self.n_owned == 0 or cnt == 0:
                 continue
             rec = self.halo_recv[base + 1:base + 1 + cnt]
-            g = rec[:, :4 * self._wf].contiguous().view(self._f).numpy()
+            g = rec[:, :4 * self._wf].clone(memory_format=self.torch.contiguous_format).view(self._f).numpy()
             glo = (g[:, :3] - g[:, 3:4]).astype(self.coord_dtype)
             ghi = (g[:, :3] + g[:, 3:4]).astype(self.coord_dtype)
             gg = rec[:, 4 * self._wf].contiguous().numpy().view(np.uint32)

@@ -1,7 +1,9 @@
 """The scene zoo: fixed-seed scenes whose VALUES are the edge cases -- radii over five decades, empty boxes, large offsets,
 coordinates that coincide, subnormal and near-overflow scales, a scene whose range overflows.  A plain helper module: the
 CPU tests pin the oracle on these scenes (tests/test_oracle_zoo.py), the GPU tests run them through every variant of the path
-(tests/test_scene_zoo.py), tools/fuzz_parity.py draws from the same definitions.
+(tests/test_scene_zoo.py) and through the multi-GPU step -- the protocol on the CPU double (tests/test_multi_zoo_cpu.py), the
+device steps of csrc/multi.hip one by one (tests/test_multi_zoo.py: rows (x, y, z, r); seed 5 gives a family's "other" rank) and
+the whole step with real engines (tests/test_multi_zoo_world.py) --, tools/fuzz_parity.py draws from the same definitions.
 
 scene(family, n, dtype, seed=4) -> (coords[n, 3], radii[n]).  Everything is drawn from one np.random.RandomState(seed) in
 float64 -- u ~ U[0,1)^3 first, then the radii -- and cast to `dtype` at the end.  s = n^(-1/3) is the mean spacing of u.
